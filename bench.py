@@ -12,8 +12,8 @@ gather of the results at the end (RCCL), outside the timed region.
   --gpus N (N > 1), default    BASELINE config 4 AS WRITTEN: 512 loops in total, 512/N per GPU
                                ("scaling": "strong"; --total-loops T changes the total).
   --gpus N --loops L           L loops PER GPU ("scaling": "weak").
-With N > 1 rank 0 afterwards times the single-GPU reference points alone (the other ranks wait)
-and the line carries both efficiencies of SURVEY.md 8e:
+With N > 1 and --full rank 0 afterwards times the single-GPU reference points alone (the other ranks
+wait) and the line carries both efficiencies of SURVEY.md 8e:
   eff_w = T(N, total) / (N * T(1, total/N))   same per-GPU load   (what the >= 0.9 target uses)
   eff_s = T(N, total) / (N * T(1, total))     same total problem
 `python bench.py --gpus N` from a plain shell starts its own N ranks (one process per GPU,
@@ -25,15 +25,21 @@ Schedules: `--schedule async` (default): every loop advances on its own, one fus
 loops are ready; `--schedule groups`: four groups of loops in lock-step, five launches per
 group-iteration.  Same trajectories.
 
+A plain run (`--gpus N --steps K --warmup W`) sets up, runs W warm-up steps, times EXACTLY K steps once
+(`ms_per_step` = that region / K; `value` = loops x K / that region) and prints its line.  `--full` adds everything
+else: the timed region repeated on fresh engines (`value` is then the median run), for N > 1 the weak point and rank
+0's single-GPU reference runs, for N = 1 the survey form, one figure per BASELINE config and the CPU baseline.
+`--dump-outputs DIR` writes what the first timed region computed in its last step as DIR/<name>.npy
+(`timed_outputs`); the inputs are seeded by loop id, identical from run to run.
+
 The LAST line of rank 0's stdout is the driver's record: one compact JSON line, never above 4 KB (`compact_line`),
 with BASELINE.json's metric, the `roofline` of the dominant kernel (algorithmic bytes per SURVEY.md 8d divided by the
-HIP-event duration measured on the launching stream), `roofline_flops` (secondary), `cpu_baseline` (the numpy/scipy
-oracle, which mirrors the reference's per-step structure, on this host's cores -- one single-threaded process per core
--- for a bounded sample), the efficiencies for N > 1 and one figure per BASELINE config.  Everything else -- `runs`
-(N = 1: the timed region is repeated on fresh engines while it is shorter than a second; `value` is the median run),
-`configs` (per-phase times, algorithmic bytes / FLOPs, both roofline fractions, per-repetition evaluation counts and a
-bounded CPU-oracle timing per BASELINE config), `kernels`, `phases`, `ranks` -- goes to the side file the record names
-(`detail`: bench_detail_n{N}.json beside this script and under gpurun_out/).
+HIP-event duration measured on the launching stream), `roofline_flops` (secondary), `cpu_baseline` (--full: the
+numpy/scipy oracle, which mirrors the reference's per-step structure, on this host's cores -- one single-threaded
+process per core -- for a bounded sample), the efficiencies for N > 1 and one figure per BASELINE config.  Everything
+else -- `runs`, `configs` (per-phase times, algorithmic bytes / FLOPs, both roofline fractions, per-repetition
+evaluation counts and a bounded CPU-oracle timing per BASELINE config), `kernels`, `phases`, `ranks` -- goes to the
+side file the record names (`detail`: bench_detail_n{N}.json beside this script, or in --detail-dir).
 """
 import argparse
 import json
@@ -375,6 +381,57 @@ class _DryEngine:
     def best(self):
         L = len(self.loop_ids)
         return np.zeros((L, 2)), self.loop_ids.astype(np.float64)
+
+    def observations(self):
+        L = len(self.loop_ids)
+        return np.zeros((L, self.N, 2)), np.zeros((L, self.N))
+
+    def state(self):
+        th = np.zeros((len(self.loop_ids), _counts(2, [16, 16, 1])[1]), dtype=np.float32)
+        return th, th.copy(), th.copy(), np.zeros(len(self.loop_ids), dtype=np.int64)
+
+
+DUMP_LIMIT_BYTES = 64 << 20      # --dump-outputs: all arrays together
+
+
+def timed_outputs(eng, results):
+    """What the timed path hands its caller after its last step: per loop of this rank, the point that step
+    suggested (`next_x`) and its objective value (`next_y`), the whole observation record (`X`, `y`) and the
+    classifier's weights after that step's fit (`theta`); and the gathered (loop id, best x, best y) of every rank
+    (`best_*`, rank 0)."""
+    X, y = eng.observations() if hasattr(eng, "observations") else (eng.X, eng.y)
+    out = {"loop_id": np.asarray(eng.loop_ids, dtype=np.float64),
+           "next_x": np.asarray(X[:, -1], dtype=np.float64), "next_y": np.asarray(y[:, -1], dtype=np.float64),
+           "X": np.asarray(X, dtype=np.float64), "y": np.asarray(y, dtype=np.float64)}
+    if hasattr(eng, "state"):
+        out["theta"] = np.asarray(eng.state()[0], dtype=np.float32)
+    else:                                           # (ReplicaEngine: the weights stay a device tensor)
+        out["theta"] = eng.theta.detach().cpu().numpy().astype(np.float32)
+    if results is not None:
+        results = np.asarray(results, dtype=np.float64)
+        out.update(best_loop_id=results[:, 0], best_x=results[:, 1:-1], best_y=results[:, -1])
+    return out
+
+
+def write_outputs(arrays, d, limit=DUMP_LIMIT_BYTES):
+    """DIR/<name>.npy for every array.  Above `limit` bytes in all, every per-loop array keeps the same fixed,
+    seeded sample of its rows (the loop ids of the sample are in `loop_id` / `best_loop_id`)."""
+    arrays = dict(arrays)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit:
+        frac = limit / float(total)
+        for ids, names in (("loop_id", ("loop_id", "next_x", "next_y", "X", "y", "theta")),
+                           ("best_loop_id", ("best_loop_id", "best_x", "best_y"))):
+            if ids not in arrays:
+                continue
+            n = len(arrays[ids])
+            keep = np.sort(np.random.RandomState(0).permutation(n)[:max(1, int(n * frac))])
+            for k in names:
+                arrays[k] = arrays[k][keep]
+    os.makedirs(d, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(d, f"{k}.npy"), np.ascontiguousarray(a))
+    return arrays
 
 
 def timed_run(args, loop_ids, barrier, steps=None, warmup=None):
@@ -765,11 +822,13 @@ def run_rank(args):
     wall_first = float(tmax[1])                     # engine creation + warm-up + timed steps
     runs = [dict(value=total * args.steps / float(tmax[0]), dt=float(tmax[0]), r=r)]
     results = gather_results(r["eng"], world)       # the path's only collective (RCCL gather)
+    if args.dump_outputs and rank == 0:
+        write_outputs(timed_outputs(r["eng"], results), args.dump_outputs)
     if hasattr(r["eng"], "close"):
         r["eng"].close()
     r["eng"] = None
 
-    # A timed region of K steps is tens of milliseconds here: one sample of a noisy quantity.  The
+    # A timed region of K steps is tens of milliseconds here: one sample of a noisy quantity.  With --full the
     # region (W warm-up + EXACTLY K timed steps, barriers on both sides, max over ranks) is repeated
     # on fresh engines until --min-timed-s of timed region have accumulated; `value` is the median
     # run, the line carries quartiles / min / max.  The repeat count follows from the first run's
@@ -797,12 +856,12 @@ def run_rank(args):
     st = r["st"]
 
     t_repeats_done = time.perf_counter()
-    # N > 1, config 4 as written (512 loops over the node): the same line also carries the WEAK point -- 512 loops on
+    # --full, N > 1, config 4 as written (512 loops over the node): the line also carries the WEAK point -- 512 loops on
     # EVERY GPU, what a single GPU runs for the headline -- so that one invocation per N gives the scaling curve that
     # means something for this path (eff_w: same per-GPU load) beside the as-written one (64 loops per GPU at N = 8:
     # a loop is a serial chain that an emptier GPU runs no faster).  All ranks take part; max over ranks.
     weak = None
-    if world > 1 and not args.no_efficiency and args.loops is None and args.total_loops is None:
+    if world > 1 and args.full and not args.no_efficiency and args.loops is None and args.total_loops is None:
         rw = timed_run(args, shard_loop_ids(rank, world, TOTAL_LOOPS), barrier)
         if hasattr(rw["eng"], "close"):
             rw["eng"].close()
@@ -811,9 +870,9 @@ def run_rank(args):
         weak = {"loops_per_gpu": TOTAL_LOOPS, "total_loops": TOTAL_LOOPS * world, "scaling": "weak",
                 "value": TOTAL_LOOPS * world * args.steps / float(tw[0]), "ms_per_step": 1e3 * float(tw[0]) / args.steps}
         del rw
-    # N > 1: the single-GPU reference points of the two efficiencies, timed by rank 0 ALONE
+    # --full, N > 1: the single-GPU reference points of the two efficiencies, timed by rank 0 ALONE
     eff = None
-    if world > 1 and not args.no_efficiency:
+    if world > 1 and args.full and not args.no_efficiency:
         if rank == 0:
             # (medians of repeated regions, like the N-GPU figure itself)
             n_ref = int(max(1, min(len(runs), 21)))
@@ -1046,7 +1105,7 @@ def run_rank(args):
                                       "ms_per_step": 1e3 * sv[1][1] / args.survey_steps,
                                       "N_start": int(sv[1][2]), "N_end": int(sv[1][3]),
                                       "value_is": "median of 3 fresh engines"}
-            if not args.no_configs:
+            if args.full and not args.no_configs:
                 out["configs"] = all_configs(args, solo_barrier, cpu=args.cpu_seconds > 0)
             if args.cpu_seconds > 0:                             # (rank 0 at N = 1 only)
                 allc, one = cpu_baseline(args.cpu_seconds, iters_per_loop=args.steps + args.warmup)
@@ -1175,21 +1234,28 @@ def parse_args(argv=None):
     ap.add_argument("--total-loops", type=int, default=None,
                     help=f"BO loops of the whole job, sharded over the GPUs (default {TOTAL_LOOPS} = "
                          "BASELINE config 4)")
-    ap.add_argument("--cpu-seconds", type=float, default=8.0,
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: repeated timed regions (median), the N > 1 weak point "
+                         "and single-GPU reference runs, the N = 1 survey form, per-config figures, CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step as "
+                         "DIR/<name>.npy (float64 / float32, at most 64 MB in all)")
+    ap.add_argument("--cpu-seconds", type=float, default=None,
                     help="wall seconds of the all-core CPU-oracle sample (a third of it on one core "
-                         "first); 0 = no cpu_baseline")
-    ap.add_argument("--repeats", type=int, default=0,
-                    help="timed regions on fresh engines (0 = as many as --min-timed-s asks for)")
+                         "first); 0 = no cpu_baseline (default: 8 with --full, else 0)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions on fresh engines (0 = as many as --min-timed-s asks for; "
+                         "default: 0 with --full, else 1)")
     ap.add_argument("--min-timed-s", type=float, default=1.5,
                     help="repeat the timed region until this much of it has accumulated")
     ap.add_argument("--max-repeats", type=int, default=80)
     ap.add_argument("--repeat-budget-s", type=float, default=120.0,
                     help="wall-time bound of the repeated timed regions (engine creation included)")
-    ap.add_argument("--survey-steps", type=int, default=100,
+    ap.add_argument("--survey-steps", type=int, default=None,
                     help="N = 1: also time SURVEY.md 8d's form of config 1 x 512 (T = 100 after 3 "
-                         "warm-up steps, N 13 -> 113) -> `survey_form` (0 = skip)")
+                         "warm-up steps, N 13 -> 113) -> `survey_form` (0 = skip; default: 100 with --full, else 0)")
     ap.add_argument("--no-configs", action="store_true",
-                    help="skip the per-config figures (configs 1-single-loop, 2, 3, 5)")
+                    help="--full: skip the per-config figures (configs 1-single-loop, 2, 3, 5)")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU: run the multi-rank flow (spawn, rendezvous over gloo, barriers, "
                          "gather) around an engine stand-in; the line carries \"dry_run\" and no value")
@@ -1198,7 +1264,7 @@ def parse_args(argv=None):
     ap.add_argument("--print-detail", action="store_true",
                     help="also print the full record as a line BEFORE the compact one (the compact record stays last)")
     ap.add_argument("--no-efficiency", action="store_true",
-                    help="N > 1: skip rank 0's single-GPU reference runs (eff_w / eff_s)")
+                    help="--full, N > 1: skip the weak point and rank 0's single-GPU reference runs (eff_w / eff_s)")
     ap.add_argument("--groups", type=int, default=4,
                     help="loop groups stepping on separate streams (overlaps L-BFGS-B tails)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
@@ -1219,7 +1285,13 @@ def parse_args(argv=None):
                          "are done (same trajectories)")
     ap.add_argument("--mode", default="device", choices=["device", "lockstep"],
                     help="device: L-BFGS-B restarts inside one kernel; lockstep: scipy on the host")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    # a plain run times the headline once; --full turns every other measurement on at its default
+    # (an option given explicitly holds either way)
+    for name, full, plain in (("cpu_seconds", 8.0, 0.0), ("repeats", 0, 1), ("survey_steps", 100, 0)):
+        if getattr(args, name) is None:
+            setattr(args, name, full if args.full else plain)
+    return args
 
 
 def main(argv=None):

@@ -40,7 +40,7 @@ def _record(p, detail_dir=None):
 
 
 def test_spawns_its_own_ranks_config4_as_written(tmp_path):
-    p = _run("--gpus", "2", "--dry-run", "--steps", "3", "--warmup", "1", "--detail-dir", str(tmp_path))
+    p = _run("--gpus", "2", "--dry-run", "--full", "--steps", "3", "--warmup", "1", "--detail-dir", str(tmp_path))
     assert p.returncode == 0, p.stderr[-2000:]
     d, _ = _record(p, tmp_path)
     assert d["n_gpus"] == 2 and d["steps"] == 3 and d["warmup"] == 1
@@ -61,7 +61,7 @@ def test_eight_ranks_the_drivers_widest_launch(tmp_path):
     """The N = 8 flow end to end (spawn, rendezvous, repeated regions with the same count on every
     rank, rank 0's reference points, gather): the line carries measured AND predicted efficiency
     and says how long each part of the flow took and what bounds it."""
-    p = _run("--gpus", "8", "--dry-run", "--steps", "3", "--warmup", "1", "--detail-dir", str(tmp_path), timeout=400)
+    p = _run("--gpus", "8", "--dry-run", "--full", "--steps", "3", "--warmup", "1", "--detail-dir", str(tmp_path), timeout=400)
     assert p.returncode == 0, p.stderr[-2000:]
     d, full = _record(p, tmp_path)            # the record (< 4 KB, last line) and the side file it names
     assert d["detail"].endswith("bench_detail_n8.json") and full["n_gpus"] == 8
@@ -171,9 +171,63 @@ def test_under_torch_distributed_run_as_the_driver_launches_n_ranks(tmp_path):
     port = str(29000 + os.getpid() % 2000)
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", port, os.path.join(ROOT, "bench.py"), "--gpus", "2",
-                        "--dry-run", "--steps", "2", "--warmup", "0", "--detail-dir", str(tmp_path)],
+                        "--dry-run", "--full", "--steps", "2", "--warmup", "0", "--detail-dir", str(tmp_path)],
                        env=_plain_env(), capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     d, full = _record(p, tmp_path)
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["config"]["loops_per_gpu"] == 256
     assert full["ranks"]["backend_world_size"] == 2 and "efficiency" in d
+
+
+def test_plain_run_times_the_steps_once_and_nothing_else(tmp_path):
+    """A plain run is what every change is measured with: W warm-up steps, then EXACTLY K timed steps, once.  The
+    measurements beyond the headline (repeats, weak point, reference runs, survey form, configs, CPU baseline) are
+    --full's."""
+    p = _run("--gpus", "2", "--dry-run", "--steps", "3", "--warmup", "1", "--detail-dir", str(tmp_path))
+    assert p.returncode == 0, p.stderr[-2000:]
+    d, full = _record(p, tmp_path)
+    assert d["steps"] == 3 and d["warmup"] == 1
+    assert full["runs"]["n"] == 1 and full["config"]["N_end"] - full["config"]["N_start"] == 3
+    assert d["ms_per_step"] >= 2.0              # (the stand-in engine sleeps 2 ms per step: the K steps were timed)
+    for k in ("efficiency", "weak_point_512_loops_per_gpu", "configs", "survey_form", "cpu_baseline_1core"):
+        assert k not in full, k
+    assert full["cpu_baseline"] is None
+
+
+def test_dump_outputs_writes_the_last_steps_arrays(tmp_path):
+    import numpy as np
+    out = tmp_path / "out"
+    p = _run("--gpus", "1", "--dry-run", "--steps", "2", "--warmup", "1", "--detail-dir", str(tmp_path),
+             "--dump-outputs", str(out))
+    assert p.returncode == 0, p.stderr[-2000:]
+    d = _record(p)
+    arrays = {f.name[:-4]: np.load(str(f)) for f in out.glob("*.npy")}
+    assert set(arrays) == {"loop_id", "next_x", "next_y", "X", "y", "theta", "best_loop_id", "best_x", "best_y"}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    L, N = d["config"]["loops_per_gpu"], d["config"]["N_end"]
+    assert arrays["X"].shape == (L, N, 2) and arrays["y"].shape == (L, N)
+    assert arrays["next_x"].shape == (L, 2) and arrays["next_y"].shape == (L,) and arrays["theta"].shape[0] == L
+    assert sum(f.stat().st_size for f in out.glob("*.npy")) <= 64 << 20
+
+
+def test_dump_outputs_over_the_limit_keep_a_fixed_sample(tmp_path):
+    """Above the size limit every per-loop array keeps the same seeded sample of loops, run after run."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    L, N = 1000, 40
+    ids = np.arange(L, dtype=np.float64)
+    arrays = {"loop_id": ids, "next_x": np.repeat(ids[:, None], 2, 1), "next_y": ids.copy(),
+              "X": np.repeat(ids[:, None, None], N * 2, 1).reshape(L, N, 2), "y": np.repeat(ids[:, None], N, 1),
+              "theta": np.repeat(ids[:, None], 337, 1).astype(np.float32),
+              "best_loop_id": ids.copy(), "best_x": np.repeat(ids[:, None], 2, 1), "best_y": ids.copy()}
+    limit = 200_000
+    a = bench.write_outputs(arrays, str(tmp_path / "a"), limit=limit)
+    b = bench.write_outputs(arrays, str(tmp_path / "b"), limit=limit)
+    assert sum(x.nbytes for x in a.values()) <= limit
+    for k in arrays:
+        assert np.array_equal(a[k], b[k]) and np.array_equal(np.load(str(tmp_path / "a" / f"{k}.npy")), a[k])
+    keep = a["loop_id"]
+    assert 0 < len(keep) < L and np.all(np.diff(keep) > 0)
+    for k in ("next_x", "X", "theta"):         # rows stay with their loops
+        assert np.all(a[k].reshape(len(keep), -1) == keep[:, None])

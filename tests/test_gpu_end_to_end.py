@@ -653,3 +653,38 @@ def test_config5_bf16_fit_and_argmax_chain_against_the_bf16_oracle_teacher_force
     if len(m["pick_regret_under_float64_objective"]):
         assert np.all(np.abs(m["pick_regret_under_float64_objective"]) <= 2.0 ** -7)
     assert m["none_device"] + len(m["pick_regret_under_float64_objective"]) >= n_it - m["none_oracle"]
+
+
+def test_bench_dump_outputs_are_what_the_timed_loops_computed(gpu, tmp_path):
+    """bench.py --dump-outputs on the device (what two builds of the project are compared by): the inputs are every
+    loop's seeded initial observations, each later row of the record is that loop's own suggestion with its Branin
+    value, the last step's suggestion is `next_*`, `best_*` is the record's minimum -- and a second run with the same
+    arguments writes the same arrays."""
+    import os
+    import subprocess
+    import sys
+    from bore_amd.engine import branin01, initial_state
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    L, n_init, warmup, steps = 64, 10, 1, 3
+    runs = []
+    for k in range(2):
+        out = tmp_path / f"run{k}"
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--loops", str(L),
+                            "--steps", str(steps), "--warmup", str(warmup), "--detail-dir", str(tmp_path),
+                            "--dump-outputs", str(out)], capture_output=True, text=True, timeout=300, cwd=root)
+        assert p.returncode == 0, p.stderr[-2000:]
+        runs.append({f.name[:-4]: np.load(str(f)) for f in out.glob("*.npy")})
+    a = runs[0]
+    _, _, X0, y0 = initial_state(np.arange(L), D, UNITS, 337, n_init, branin01, LOW, HIGH)
+    assert a["X"].shape == (L, n_init + warmup + steps, D) and a["theta"].shape == (L, 337)
+    np.testing.assert_array_equal(a["loop_id"], np.arange(L))
+    np.testing.assert_array_equal(a["X"][:, :n_init], X0)
+    np.testing.assert_array_equal(a["y"][:, :n_init], y0)
+    np.testing.assert_array_equal(a["next_x"], a["X"][:, -1])
+    np.testing.assert_array_equal(a["next_y"], a["y"][:, -1])
+    np.testing.assert_allclose(a["y"][:, n_init:], branin01(a["X"][:, n_init:]), rtol=1e-10, atol=1e-12)
+    assert np.all((a["X"] >= 0.0) & (a["X"] <= 1.0)) and np.all(np.isfinite(a["theta"]))
+    np.testing.assert_array_equal(a["best_y"], a["y"].min(axis=1))
+    assert set(runs[1]) == set(a)
+    for k in a:
+        np.testing.assert_array_equal(runs[1][k], a[k], err_msg=k)

@@ -9,9 +9,9 @@ O=$R/gpurun_out
 export TMPDIR=/tmp
 cd $R
 HEAD="--steps 20 --warmup 5 --cpu-seconds 0 --no-configs --repeats 1 --survey-steps 0"   # the driver's headline run, once
-echo "== bench as the driver runs it"; timeout -k 10 500 python3 bench.py --steps 20 --warmup 5 > $O/${tag}_bench_driver.json 2> $O/${tag}_bench_driver.err || exit 1
+echo "== bench, the full record"; timeout -k 10 500 python3 bench.py --full --steps 20 --warmup 5 > $O/${tag}_bench_driver.json 2> $O/${tag}_bench_driver.err || exit 1
 tail -c 300 $O/${tag}_bench_driver.json; echo
-echo "== bench, SURVEY workload (T = 100)"; timeout -k 10 300 python3 bench.py --steps 100 --warmup 3 --cpu-seconds 0 --no-configs --survey-steps 0 > $O/${tag}_bench_T100.json 2>/dev/null || exit 1
+echo "== bench, SURVEY workload (T = 100)"; timeout -k 10 300 python3 bench.py --full --steps 100 --warmup 3 --cpu-seconds 0 --no-configs --survey-steps 0 > $O/${tag}_bench_T100.json 2>/dev/null || exit 1
 echo "== rocprofv3 kernel trace: headline"
 rm -rf $O/prof_${tag}_kt
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_${tag}_kt --output-format csv -- python3 bench.py $HEAD > $O/${tag}_bench_under_rocprof.json 2> $O/${tag}_rocprof_kt.err || exit 1
@@ -27,7 +27,7 @@ rm -rf $O/prof_${tag}_sq
 timeout -k 10 300 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAIT_ANY SQ_ACTIVE_INST_ANY -d $O/prof_${tag}_sq --output-format csv -- python3 bench.py $HEAD > /dev/null 2> $O/${tag}_rocprof_sq.err || exit 1
 python3 tools/prof_summary.py $O/prof_${tag}_sq $O/${tag}_headline_sq | tail -6
 # the other BASELINE configs (2, 3, 5): bench.py's `configs` leg under the profiler
-CFG="--steps 2 --warmup 1 --cpu-seconds 0 --repeats 1 --survey-steps 0"
+CFG="--full --steps 2 --warmup 1 --cpu-seconds 0 --repeats 1 --survey-steps 0"
 echo "== rocprofv3 kernel trace: configs 2 / 3 / 5"
 rm -rf $O/prof_${tag}_cfg_kt
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof_${tag}_cfg_kt --output-format csv -- python3 bench.py $CFG > $O/${tag}_bench_cfg_under_rocprof.json 2> $O/${tag}_rocprof_cfg_kt.err || exit 1

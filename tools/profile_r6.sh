@@ -9,10 +9,10 @@ O=$R/gpurun_out
 export TMPDIR=/tmp
 cd $R
 HEAD="--steps 20 --warmup 5 --cpu-seconds 0 --no-configs --repeats 1 --survey-steps 0"   # the driver's headline run, once
-echo "== bench as the driver runs it"; timeout -k 10 500 python3 bench.py --steps 20 --warmup 5 --detail-dir $O > $O/${tag}_bench_driver_line.json 2> $O/${tag}_bench_driver.err || exit 1
+echo "== bench, the full record"; timeout -k 10 500 python3 bench.py --full --steps 20 --warmup 5 --detail-dir $O > $O/${tag}_bench_driver_line.json 2> $O/${tag}_bench_driver.err || exit 1
 cp $O/bench_detail_n1.json $O/${tag}_bench_driver.json
 tail -n 1 $O/${tag}_bench_driver_line.json | cut -c1-400; echo; tail -n 1 $O/${tag}_bench_driver_line.json | wc -c
-echo "== bench, SURVEY workload (T = 100)"; timeout -k 10 300 python3 bench.py --steps 100 --warmup 3 --cpu-seconds 0 --no-configs --survey-steps 0 --detail-dir $O > /dev/null 2>/dev/null || exit 1
+echo "== bench, SURVEY workload (T = 100)"; timeout -k 10 300 python3 bench.py --full --steps 100 --warmup 3 --cpu-seconds 0 --no-configs --survey-steps 0 --detail-dir $O > /dev/null 2>/dev/null || exit 1
 cp $O/bench_detail_n1.json $O/${tag}_bench_T100.json
 echo "== rocprofv3 kernel trace: headline"
 rm -rf $O/prof_${tag}_kt
@@ -33,7 +33,7 @@ echo "== rocprofv3 --pmc SQ (second set): headline"
 rm -rf $O/prof_${tag}_sq2
 timeout -k 10 300 rocprofv3 --pmc SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_SCA SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_INST_CYCLES_VMEM SQ_INSTS_SMEM SQ_INSTS_VMEM -d $O/prof_${tag}_sq2 --output-format csv -- python3 bench.py $HEAD > /dev/null 2> $O/${tag}_rocprof_sq2.err && python3 tools/prof_summary.py $O/prof_${tag}_sq2 $O/${tag}_headline_sq2 | tail -6 || echo "(second SQ set not collected: see ${tag}_rocprof_sq2.err)"
 # the other BASELINE configs (2, 3, 5): bench.py's `configs` leg under the profiler
-CFG="--steps 2 --warmup 1 --cpu-seconds 0 --repeats 1 --survey-steps 0"
+CFG="--full --steps 2 --warmup 1 --cpu-seconds 0 --repeats 1 --survey-steps 0"
 echo "== rocprofv3 kernel trace: configs 2 / 3 / 5"
 rm -rf $O/prof_${tag}_cfg_kt
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof_${tag}_cfg_kt --output-format csv -- python3 bench.py $CFG --detail-dir $O > /dev/null 2> $O/${tag}_rocprof_cfg_kt.err || exit 1
