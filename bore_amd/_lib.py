@@ -40,6 +40,8 @@ EXPORTS = [
     "bore_lbfgsb_minimize", "bore_append_observations", "bore_select_best",
     "bore_svgd_optimize", "bore_set_batch", "bore_engine_create", "bore_engine_run", "bore_engine_size", "bore_engine_observations",
     "bore_engine_state", "bore_engine_get_stats", "bore_engine_destroy", "bore_objective_branin01",
+    "bore_lstm_param_count", "bore_lstm_forward", "bore_lstm_value_and_input_grad", "bore_lstm_fit",
+    "bore_lstm_evaluate",
 ]
 
 
@@ -48,6 +50,17 @@ class MlpDesc(C.Structure):
                 ("units", C.c_int32 * MAX_LAYERS), ("act", C.c_int32 * MAX_LAYERS),
                 ("l2_kernel", C.c_float * MAX_LAYERS), ("l2_bias", C.c_float * MAX_LAYERS),
                 ("compute", C.c_int32)]
+
+
+LSTM_MAX_LAYERS = 4      # include/bore_hip.h BORE_LSTM_MAX_*
+LSTM_MAX_STEPS = 16
+
+
+class LstmDesc(C.Structure):
+    """bore_lstm_desc: l2 factors per cell, index ``n_layers`` = the Dense head."""
+    _fields_ = [("input_dim", C.c_int32), ("n_layers", C.c_int32), ("units", C.c_int32),
+                ("act", C.c_int32), ("l2_kernel", C.c_float * (LSTM_MAX_LAYERS + 1)),
+                ("l2_bias", C.c_float * (LSTM_MAX_LAYERS + 1)), ("output_dim", C.c_int32)]
 
 
 class LbfgsbOpts(C.Structure):
@@ -221,8 +234,16 @@ def lib():
     L.bore_engine_state.argtypes = [vp, vp, vp, vp, vp]
     L.bore_engine_get_stats.argtypes = [vp, C.POINTER(EngineStats), i32]
     L.bore_engine_destroy.argtypes = [vp]
+    lp, f32 = C.POINTER(LstmDesc), C.c_float
+    L.bore_lstm_param_count.restype = i64
+    L.bore_lstm_param_count.argtypes = [lp]
+    L.bore_lstm_forward.argtypes = [lp, i32, vp, vp, i64, i32, i32, f32, vp, vp]
+    L.bore_lstm_value_and_input_grad.argtypes = [lp, i32, vp, vp, i64, i32, i32, i32, vp, vp, vp]
+    L.bore_lstm_fit.argtypes = [lp, i32, vp, vp, vp, vp, vp, vp, i64, i32, f32, i32, i32, vp,
+                                C.POINTER(AdamCfg), vp, vp]
+    L.bore_lstm_evaluate.argtypes = [lp, i32, vp, vp, vp, i64, i32, f32, vp, vp, vp]
     for name in EXPORTS:
-        if name not in ("bore_last_error", "bore_param_count", "bore_engine_size",
+        if name not in ("bore_last_error", "bore_param_count", "bore_lstm_param_count", "bore_engine_size",
                         "bore_engine_destroy", "bore_set_batch"):
             getattr(L, name).restype = i32
     L.bore_engine_size.restype = i64
@@ -269,6 +290,25 @@ def make_desc(input_dim, units, acts, l2_kernel=None, l2_bias=None, compute="flo
         d.l2_kernel[i] = float(l2_kernel[i]) if l2_kernel and l2_kernel[i] else 0.0
         d.l2_bias[i] = float(l2_bias[i]) if l2_bias and l2_bias[i] else 0.0
     d.compute = COMPUTE[compute]
+    return d
+
+
+def make_lstm_desc(input_dim, n_layers, units, act, l2_kernel=None, l2_bias=None, output_dim=1):
+    """bore_lstm_desc.  ``l2_kernel`` / ``l2_bias``: n_layers factors (the cells), optionally one more (the head)."""
+    if not 1 <= int(n_layers) <= LSTM_MAX_LAYERS:
+        raise UnsupportedError(f"1..{LSTM_MAX_LAYERS} LSTM layers supported (BORE_LSTM_MAX_LAYERS), got {n_layers}")
+    a = act if act is not None else "linear"
+    if a not in ACT:
+        raise ValueError(f"unsupported activation {a!r}; supported: {sorted(ACT)}")
+    d = LstmDesc()
+    d.input_dim, d.n_layers, d.units, d.act = int(input_dim), int(n_layers), int(units), ACT[a]
+    d.output_dim = int(output_dim)
+    for name, vals in (("l2_kernel", l2_kernel), ("l2_bias", l2_bias)):
+        arr = getattr(d, name)
+        for i, f in enumerate(vals or []):
+            if i > LSTM_MAX_LAYERS:
+                raise ValueError(f"{name}: at most n_layers + 1 factors")
+            arr[i] = float(f) if f else 0.0
     return d
 
 

@@ -26,6 +26,12 @@ def convert(model, transform=None):
     bore/decorators.py:54-61).  Returns a 2-element list like ``numpy_io`` does
     (bore/decorators.py:75-77)."""
     tr = resolve(transform)
+    # a network with a kernel of its own (the one-to-one LSTM network) names it; Dense stacks have none
+    hook = getattr(type(model), "_value_and_input_grad", None)
+    if hook is not None:
+        vg = lambda Xd, name, negate: model._value_and_input_grad(Xd, name, negate)  # noqa: E731
+    else:
+        vg = lambda Xd, name, negate: ops.mlp_value_and_input_grad(model._desc, model.theta, Xd, name, negate)  # noqa: E731
 
     def fn(x):
         x = np.asarray(x, dtype=np.float64)
@@ -36,11 +42,11 @@ def convert(model, transform=None):
         if isinstance(tr, CallableTransform):
             # f and d f / d x from the kernel; the callable and its derivative on the host (float32
             # value, float64 gradient, like numpy_io / value_and_gradient: bore/decorators.py:51-77)
-            f, gf = ops.mlp_value_and_input_grad(model._desc, model.theta, Xd, "identity", False)
+            f, gf = vg(Xd, "identity", False)
             val, dT = tr.value_and_derivative(f[0].cpu().numpy())
             grad = dT[:, None] * gf[0].cpu().numpy()
         else:
-            val, grad = ops.mlp_value_and_input_grad(model._desc, model.theta, Xd, tr.name, tr.negate)
+            val, grad = vg(Xd, tr.name, tr.negate)
             val = val[0].cpu().numpy()
             grad = grad[0].cpu().numpy()
         if single:

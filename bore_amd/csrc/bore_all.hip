@@ -6,3 +6,4 @@
 #include "bore_svgd.hip"
 #include "bore_iter.hip"
 #include "bore_engine.hip"
+#include "bore_lstm.hip"

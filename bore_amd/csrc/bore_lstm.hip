@@ -1,0 +1,749 @@
+// bore_lstm.hip -- the multi-fidelity classifier of the reference (bore/models.py:48-104,
+// StackedRecurrentFactory): a stack of Keras LSTMCells and a Dense(1) head, run over the rungs of a
+// Hyperband ladder.  Entry points: bore_lstm_param_count / _forward / _value_and_input_grad / _fit /
+// _evaluate (include/bore_hip.h).  Included from bore_all.hip.
+//
+// One scheme for every entry point: a workgroup of LSTM_NT threads takes a TILE of up to 64 sequences
+// and walks them through time, layer after layer, with the packed parameters in LDS (rows of W and U
+// padded to 4H + 1 floats, so the transposed products of the backward pass are free of bank
+// conflicts).  Work inside a (step, layer) phase is split over (sequence, unit) items: one thread
+// forms the four gate sums of its unit, in a fixed order, so that every form of the forward pass --
+// many-to-many, one-to-one, inside the fit -- gives the same bits for the same inputs.  A masked step
+// keeps h and c (Keras RNN with a Masking layer, TF 2.5): chosen by select, never by a branch per row.
+// The backward pass (fit, input gradient) reads the activations of the whole sequence back from a
+// per-tile device workspace (stream-ordered, hipMallocAsync), accumulates the weight gradients of an
+// Adam step in a per-model device buffer in a fixed order, and updates theta (LDS), m and v (memory)
+// once per step -- every Adam step of a call inside one launch, as the Dense fit does.
+#include "host_common.h"
+
+namespace bore_lstm {
+
+constexpr int NT = 512;           // threads per workgroup (8 waves)
+constexpr int TILE = 64;          // sequences per tile (batch_size <= 64)
+constexpr int MAXL = BORE_LSTM_MAX_LAYERS;
+constexpr int MAXH = BORE_LSTM_MAX_UNITS;
+constexpr int MAXT = BORE_LSTM_MAX_STEPS;
+constexpr int MAXD = BORE_LSTM_MAX_INPUT;
+constexpr int MAXITEMS = TILE * MAXH / NT;  // (sequence, unit) items per thread
+
+struct Lay {
+  int D, L, H, act, T, G, G1;  // G = 4H, G1 = padded row of W / U in LDS
+  int P;
+  int in_dim[MAXL];
+  int gW[MAXL], gU[MAXL], gb[MAXL], gWo, gbo;  // offsets in the packed vector (get_weights order)
+  int sW[MAXL], sU[MAXL], sb[MAXL], sWo, sbo;  // offsets in LDS
+  int o_h, o_c, o_dz, o_din, o_dx, o_logit, o_dlogit, o_mask, o_red, o_rows, lds_floats;
+  float l2k[MAXL + 1], l2b[MAXL + 1];  // index L: the Dense head
+  long long ws_floats;                 // activations of one tile: gates [L][T][64][4H], c, h [L][T][64][H]
+};
+
+// --------------------------------------------------------------------------------------------------
+// host: descriptor -> layout
+// --------------------------------------------------------------------------------------------------
+static int make_lay(const bore_lstm_desc *d, int T, Lay *y) {
+  if (!d) return fail(BORE_E_INVALID, "lstm: null descriptor");
+  if (d->output_dim != 1)
+    return fail(BORE_E_UNSUPPORTED, "lstm: output_dim must be 1 (the BORE classifier), got %d", d->output_dim);
+  if (d->input_dim < 1 || d->n_layers < 1 || d->units < 1)
+    return fail(BORE_E_INVALID, "lstm: input_dim, n_layers and units must be positive (got %d, %d, %d)",
+                d->input_dim, d->n_layers, d->units);
+  if (d->act < BORE_ACT_LINEAR || d->act > BORE_ACT_TANH)
+    return fail(BORE_E_INVALID, "lstm: unknown activation %d", d->act);
+  if (d->input_dim > MAXD)
+    return fail(BORE_E_UNSUPPORTED, "lstm: input_dim %d > %d (BORE_LSTM_MAX_INPUT)", d->input_dim, MAXD);
+  if (d->n_layers > MAXL)
+    return fail(BORE_E_UNSUPPORTED, "lstm: n_layers %d > %d (BORE_LSTM_MAX_LAYERS)", d->n_layers, MAXL);
+  if (d->units > MAXH)
+    return fail(BORE_E_UNSUPPORTED, "lstm: units %d > %d (BORE_LSTM_MAX_UNITS)", d->units, MAXH);
+  if (T < 0 || T > MAXT)
+    return fail(BORE_E_UNSUPPORTED, "lstm: %d steps > %d (BORE_LSTM_MAX_STEPS)", T, MAXT);
+  Lay &a = *y;
+  a.D = d->input_dim; a.L = d->n_layers; a.H = d->units; a.act = d->act; a.T = T < 1 ? 1 : T;
+  a.G = 4 * a.H; a.G1 = a.G + 1;
+  long long g = 0, s = 0;
+  for (int l = 0; l < a.L; ++l) {
+    const int in = l == 0 ? a.D : a.H;
+    a.in_dim[l] = in;
+    a.gW[l] = (int)g; g += (long long)in * a.G;
+    a.gU[l] = (int)g; g += (long long)a.H * a.G;
+    a.gb[l] = (int)g; g += a.G;
+    a.sW[l] = (int)s; s += (long long)in * a.G1;
+    a.sU[l] = (int)s; s += (long long)a.H * a.G1;
+    a.sb[l] = (int)s; s += a.G;
+    a.l2k[l] = d->l2_kernel[l]; a.l2b[l] = d->l2_bias[l];
+  }
+  a.gWo = (int)g; g += a.H; a.gbo = (int)g; g += 1;
+  a.sWo = (int)s; s += a.H; a.sbo = (int)s; s += 1;
+  a.l2k[a.L] = d->l2_kernel[a.L]; a.l2b[a.L] = d->l2_bias[a.L];
+  a.P = (int)g;
+  s = (s + 3) & ~3LL;
+  const int Dm = a.D > a.H ? a.D : a.H;
+  a.o_h = (int)s; s += (long long)a.L * TILE * a.H;
+  a.o_c = (int)s; s += (long long)a.L * TILE * a.H;
+  a.o_dz = (int)s; s += (long long)TILE * a.G;
+  a.o_din = (int)s; s += (long long)TILE * Dm;
+  a.o_dx = (int)s; s += (long long)TILE * a.D;
+  a.o_logit = (int)s; s += (long long)TILE * a.T;
+  a.o_dlogit = (int)s; s += (long long)TILE * a.T;
+  a.o_mask = (int)s; s += (long long)TILE * a.T;
+  a.o_red = (int)s; s += NT;
+  a.o_rows = (int)s; s += TILE;
+  a.lds_floats = (int)s;
+  if (s * 4 > BORE_LDS_BYTES)
+    return fail(BORE_E_UNSUPPORTED,
+                "lstm: %d inputs, %d layers of %d units over %d steps need %lld B of LDS per workgroup "
+                "(> %d): parameters (%d floats) and one tile of state must fit one CU",
+                a.D, a.L, a.H, a.T, s * 4, BORE_LDS_BYTES, a.P);
+  a.ws_floats = (long long)a.L * a.T * TILE * (a.G + 2 * a.H);
+  return 0;
+}
+
+// --------------------------------------------------------------------------------------------------
+// device
+// --------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float sig(float x) {
+  const float e = expf(-fabsf(x));
+  const float d = 1.f + e;
+  return x >= 0.f ? 1.f / d : e / d;
+}
+
+// act(x); elu through expm1f for x <= 0, NaN in -> NaN out
+__device__ __forceinline__ float actf(int a, float x) {
+  switch (a) {
+    case BORE_ACT_RELU: return x > 0.f ? x : (x == x ? 0.f : x);
+    case BORE_ACT_ELU: return x > 0.f ? x : expm1f(x);
+    case BORE_ACT_SIGMOID: return sig(x);
+    case BORE_ACT_TANH: return tanhf(x);
+    default: return x;
+  }
+}
+
+// d act / d pre-activation from the activation's OUTPUT h (as oracle/bore_oracle.py writes it)
+__device__ __forceinline__ float actg(int a, float h) {
+  switch (a) {
+    case BORE_ACT_RELU: return h > 0.f ? 1.f : 0.f;
+    case BORE_ACT_ELU: return h > 0.f ? 1.f : h + 1.f;
+    case BORE_ACT_SIGMOID: return h * (1.f - h);
+    case BORE_ACT_TANH: return 1.f - h * h;
+    default: return 1.f;
+  }
+}
+
+// LDS address of packed parameter p
+__device__ __forceinline__ int lds_of(const Lay &a, int p) {
+  for (int l = 0; l < a.L; ++l) {
+    if (p < a.gU[l] && p >= a.gW[l]) { const int q = p - a.gW[l]; return a.sW[l] + (q / a.G) * a.G1 + q % a.G; }
+    if (p < a.gb[l] && p >= a.gU[l]) { const int q = p - a.gU[l]; return a.sU[l] + (q / a.G) * a.G1 + q % a.G; }
+    if (p < a.gb[l] + a.G && p >= a.gb[l]) return a.sb[l] + (p - a.gb[l]);
+  }
+  return a.sWo + (p - a.gWo);  // (Wo and bo are adjacent in both)
+}
+
+// l2 factor of packed parameter p (never U: Keras' recurrent_regularizer is not set)
+__device__ __forceinline__ float l2_of(const Lay &a, int p) {
+  for (int l = 0; l < a.L; ++l) {
+    if (p < a.gU[l] && p >= a.gW[l]) return a.l2k[l];
+    if (p < a.gb[l] && p >= a.gU[l]) return 0.f;
+    if (p < a.gb[l] + a.G && p >= a.gb[l]) return a.l2b[l];
+  }
+  return p == a.gbo ? a.l2b[a.L] : a.l2k[a.L];
+}
+
+__device__ __forceinline__ void load_theta(const Lay &a, const float *__restrict__ g, float *sm) {
+  for (int p = threadIdx.x; p < a.P; p += NT) sm[lds_of(a, p)] = g[p];
+}
+
+// fixed-order sum over the workgroup (tree over the LSTM_NT slots); every thread gets the result
+__device__ __forceinline__ float block_sum(float v, float *red) {
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int s = NT / 2; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  const float r = red[0];
+  __syncthreads();
+  return r;
+}
+
+// Where a tile's inputs come from.  X points at [rows][T][D] (x_step = D) or at [rows][D] repeated
+// over the steps (x_step = 0, RepeatVector of the one-to-one net); rows[b] is the row of sequence b.
+template <typename XT>
+struct Src {
+  const XT *X;
+  long long row_stride;
+  int x_step;
+  __device__ __forceinline__ float x(const int *rows, int b, int t, int k) const {
+    return (float)X[(long long)rows[b] * row_stride + (long long)t * x_step + k];
+  }
+};
+
+// mask[b][t] = 1 iff any feature of step t differs from mask_value (Keras Masking); use_mask = 0: all live
+template <typename XT>
+__device__ void make_mask(const Lay &a, const Src<XT> &src, const int *rows, int nrows, int T, int use_mask,
+                          float mask_value, float *mask) {
+  for (int it = threadIdx.x; it < nrows * T; it += NT) {
+    const int b = it / T, t = it % T;
+    bool live = !use_mask;
+    if (use_mask)
+      for (int k = 0; k < a.D; ++k) live |= src.x(rows, b, t, k) != mask_value;
+    mask[b * T + t] = live ? 1.f : 0.f;
+  }
+}
+
+// Forward pass of one tile over T steps: logits [b][t] in LDS; with ws, the activations for backward.
+template <typename XT>
+__device__ void tile_forward(const Lay &a, float *sm, const Src<XT> &src, int nrows, int T, float *ws) {
+  const int H = a.H, G = a.G, G1 = a.G1, L = a.L;
+  const int *rows = reinterpret_cast<const int *>(sm + a.o_rows);
+  const float *mask = sm + a.o_mask;
+  float *hS = sm + a.o_h, *cS = sm + a.o_c, *logit = sm + a.o_logit;
+  for (int i = threadIdx.x; i < L * TILE * H; i += NT) hS[i] = cS[i] = 0.f;
+  __syncthreads();
+  const int n_items = nrows * H;
+  for (int t = 0; t < T; ++t) {
+    for (int l = 0; l < L; ++l) {
+      const int in_dim = a.in_dim[l];
+      const float *W = sm + a.sW[l], *U = sm + a.sU[l], *bias = sm + a.sb[l];
+      float *hl = hS + l * TILE * H, *cl = cS + l * TILE * H;
+      const float *hin = l > 0 ? hS + (l - 1) * TILE * H : hS;  // (l > 0: layer l-1 at this step)
+      float hn[MAXITEMS], cn[MAXITEMS];
+#pragma unroll
+      for (int q = 0; q < MAXITEMS; ++q) {
+        const int it = threadIdx.x + q * NT;
+        if (it >= n_items) break;
+        const int b = it / H, u = it % H;
+        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;  // x . W
+        for (int k = 0; k < in_dim; ++k) {
+          const float xv = l == 0 ? src.x(rows, b, t, k) : hin[b * H + k];
+          const float *w = W + k * G1 + u;
+          s0 = fmaf(xv, w[0], s0); s1 = fmaf(xv, w[H], s1); s2 = fmaf(xv, w[2 * H], s2); s3 = fmaf(xv, w[3 * H], s3);
+        }
+        float r0 = 0.f, r1 = 0.f, r2 = 0.f, r3 = 0.f;  // h . U
+        for (int k = 0; k < H; ++k) {
+          const float hv = hl[b * H + k];
+          const float *w = U + k * G1 + u;
+          r0 = fmaf(hv, w[0], r0); r1 = fmaf(hv, w[H], r1); r2 = fmaf(hv, w[2 * H], r2); r3 = fmaf(hv, w[3 * H], r3);
+        }
+        const float gi = sig((s0 + r0) + bias[u]);
+        const float gf = sig((s1 + r1) + bias[H + u]);
+        const float gg = actf(a.act, (s2 + r2) + bias[2 * H + u]);
+        const float go = sig((s3 + r3) + bias[3 * H + u]);
+        const float cp = cl[b * H + u], hp = hl[b * H + u];
+        const float c = gf * cp + gi * gg;
+        const float h = go * actf(a.act, c);
+        const bool live = mask[b * T + t] != 0.f;
+        cn[q] = live ? c : cp;
+        hn[q] = live ? h : hp;
+        if (ws) {
+          float *gw = ws + (((long long)l * a.T + t) * TILE + b) * G;
+          gw[u] = gi; gw[H + u] = gf; gw[2 * H + u] = gg; gw[3 * H + u] = go;
+        }
+      }
+      __syncthreads();
+#pragma unroll
+      for (int q = 0; q < MAXITEMS; ++q) {
+        const int it = threadIdx.x + q * NT;
+        if (it >= n_items) break;
+        hl[it] = hn[q];
+        cl[it] = cn[q];
+        if (ws) {
+          const long long base = (long long)L * a.T * TILE * G;
+          const long long o = ((long long)l * a.T + t) * TILE * H + it;
+          ws[base + o] = cn[q];                               // c history
+          ws[base + (long long)L * a.T * TILE * H + o] = hn[q];  // h history
+        }
+      }
+      __syncthreads();
+    }
+    // Dense head on the top layer's output
+    const float *Wo = sm + a.sWo, bo = sm[a.sbo];
+    const float *ht = hS + (L - 1) * TILE * H;
+    for (int b = threadIdx.x; b < nrows; b += NT) {
+      float s = 0.f;
+      for (int k = 0; k < H; ++k) s = fmaf(ht[b * H + k], Wo[k], s);
+      logit[b * T + t] = s + bo;
+    }
+  }
+  __syncthreads();
+}
+
+__device__ __forceinline__ const float *ws_c(const Lay &a, const float *ws, int l, int t) {
+  return ws + (long long)a.L * a.T * TILE * a.G + ((long long)l * a.T + t) * TILE * a.H;
+}
+__device__ __forceinline__ const float *ws_h(const Lay &a, const float *ws, int l, int t) {
+  return ws + (long long)a.L * a.T * TILE * (a.G + a.H) + ((long long)l * a.T + t) * TILE * a.H;
+}
+
+// Backpropagation through time of one tile, from dlogit [b][t] (LDS).  gacc != null: adds the weight
+// gradients to gacc (packed order); want_dx: dx [b][k] (LDS) = d/dx summed over the steps.
+template <typename XT>
+__device__ void tile_backward(const Lay &a, float *sm, const Src<XT> &src, int nrows, int T, const float *ws,
+                              float *gacc, bool want_dx) {
+  const int H = a.H, G = a.G, G1 = a.G1, L = a.L;
+  const int *rows = reinterpret_cast<const int *>(sm + a.o_rows);
+  const float *mask = sm + a.o_mask, *dlogit = sm + a.o_dlogit;
+  float *dhS = sm + a.o_h, *dcS = sm + a.o_c, *dz = sm + a.o_dz, *din = sm + a.o_din, *dx = sm + a.o_dx;
+  const float *Wo = sm + a.sWo;
+  for (int i = threadIdx.x; i < L * TILE * H; i += NT) dhS[i] = dcS[i] = 0.f;
+  if (want_dx)
+    for (int i = threadIdx.x; i < TILE * a.D; i += NT) dx[i] = 0.f;
+  // the head: dWo[k] = sum_t sum_b dlogit h_top, dbo = sum dlogit
+  if (gacc) {
+    for (int k = threadIdx.x; k <= H; k += NT) {
+      float s = 0.f;
+      for (int t = T - 1; t >= 0; --t) {
+        const float *ht = ws_h(a, ws, L - 1, t);
+        for (int b = 0; b < nrows; ++b) s = fmaf(dlogit[b * T + t], k < H ? ht[b * H + k] : 1.f, s);
+      }
+      gacc[a.gWo + k] += s;
+    }
+  }
+  __syncthreads();
+  const int n_items = nrows * H;
+  for (int t = T - 1; t >= 0; --t) {
+    for (int l = L - 1; l >= 0; --l) {
+      const int in_dim = a.in_dim[l];
+      float *dhl = dhS + l * TILE * H, *dcl = dcS + l * TILE * H;
+      const float *gts = ws + ((long long)l * a.T + t) * TILE * G;
+      const float *ct = ws_c(a, ws, l, t);
+      const float *cpv = t > 0 ? ws_c(a, ws, l, t - 1) : nullptr;
+      // phase A: the gate deltas of (sequence, unit) items
+      for (int it = threadIdx.x; it < n_items; it += NT) {
+        const int b = it / H, u = it % H;
+        const float above = l == L - 1 ? dlogit[b * T + t] * Wo[u] : din[b * H + u];
+        const float dh = dhl[it] + above;
+        const float dcin = dcl[it];
+        const bool live = mask[b * T + t] != 0.f;
+        const float *g = gts + b * G;
+        const float gi = g[u], gf = g[H + u], gg = g[2 * H + u], go = g[3 * H + u];
+        const float c = ct[it], cp = cpv ? cpv[it] : 0.f;
+        const float ac = actf(a.act, c);
+        const float dct = dcin + dh * go * actg(a.act, ac);
+        const float dzi = dct * gg * (gi * (1.f - gi));
+        const float dzf = dct * cp * (gf * (1.f - gf));
+        const float dzg = dct * gi * actg(a.act, gg);
+        const float dzo = dh * ac * (go * (1.f - go));
+        float *d = dz + b * G;
+        d[u] = live ? dzi : 0.f;
+        d[H + u] = live ? dzf : 0.f;
+        d[2 * H + u] = live ? dzg : 0.f;
+        d[3 * H + u] = live ? dzo : 0.f;
+        dcl[it] = live ? dct * gf : dcin;
+        if (!live) dhl[it] = dh;  // (a masked step passes h's gradient to the step before)
+      }
+      __syncthreads();
+      // phase B: recurrent delta, delta of the layer below, weight gradients
+      const float *W = sm + a.sW[l], *U = sm + a.sU[l];
+      for (int it = threadIdx.x; it < n_items; it += NT) {
+        const int b = it / H, k = it % H;
+        if (mask[b * T + t] == 0.f) continue;
+        const float *d = dz + b * G, *w = U + k * G1;
+        float s = 0.f;
+        for (int j = 0; j < G; ++j) s = fmaf(d[j], w[j], s);
+        dhl[it] = s;
+      }
+      if (l > 0 || want_dx) {
+        for (int it = threadIdx.x; it < nrows * in_dim; it += NT) {
+          const int b = it / in_dim, k = it % in_dim;
+          const float *d = dz + b * G, *w = W + k * G1;
+          float s = 0.f;
+          for (int j = 0; j < G; ++j) s = fmaf(d[j], w[j], s);
+          if (l > 0) din[b * H + k] = s;
+          else dx[b * a.D + k] += s;
+        }
+      }
+      if (gacc) {
+        const float *hin = l > 0 ? ws_h(a, ws, l - 1, t) : nullptr;
+        const float *hpv = t > 0 ? ws_h(a, ws, l, t - 1) : nullptr;
+        const int n_w = (in_dim + H + 1) * G;  // rows of W, rows of U, the bias
+        for (int it = threadIdx.x; it < n_w; it += NT) {
+          const int r = it / G, j = it % G;
+          float s = 0.f;
+          if (r < in_dim) {
+            for (int b = 0; b < nrows; ++b)
+              s = fmaf(l > 0 ? hin[b * H + r] : src.x(rows, b, t, r), dz[b * G + j], s);
+            gacc[a.gW[l] + r * G + j] += s;
+          } else if (r < in_dim + H) {
+            if (hpv) {
+              for (int b = 0; b < nrows; ++b) s = fmaf(hpv[b * H + (r - in_dim)], dz[b * G + j], s);
+              gacc[a.gU[l] + (r - in_dim) * G + j] += s;
+            }
+          } else {
+            for (int b = 0; b < nrows; ++b) s += dz[b * G + j];
+            gacc[a.gb[l] + j] += s;
+          }
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// BCE from logits of one tile (per element max(a,0) - a y + log1p(exp(-|a|)), weighted by the mask),
+// dlogit = mask (sigmoid(a) - y) / (nrows T); returns the weighted sum of the element losses.
+__device__ float tile_bce(const Lay &a, float *sm, const float *Y, long long y_stride, int nrows, int T,
+                          float scale) {
+  const int *rows = reinterpret_cast<const int *>(sm + a.o_rows);
+  const float *mask = sm + a.o_mask, *logit = sm + a.o_logit;
+  float *dlogit = sm + a.o_dlogit;
+  float part = 0.f;
+  for (int it = threadIdx.x; it < nrows * T; it += NT) {
+    const int b = it / T, t = it % T;
+    const float x = logit[it], y = Y[(long long)rows[b] * y_stride + t];
+    const bool live = mask[it] != 0.f;
+    const float l = fmaxf(x, 0.f) - x * y + log1pf(expf(-fabsf(x)));
+    part += live ? l : 0.f;
+    dlogit[it] = live ? (sig(x) - y) * scale : 0.f;
+  }
+  return block_sum(part, sm + a.o_red);
+}
+
+// --------------------------------------------------------------------------------------------------
+// kernels
+// --------------------------------------------------------------------------------------------------
+struct FwdArgs {
+  Lay a;
+  const float *theta, *X;
+  long long n;
+  int T, m2m, use_mask;
+  float mask_value;
+  float *out;
+};
+
+__global__ void __launch_bounds__(NT) lstm_forward_kernel(FwdArgs A) {
+  extern __shared__ float sm[];
+  const Lay &a = A.a;
+  const int m = blockIdx.y;
+  const long long r0 = (long long)blockIdx.x * TILE;
+  const int nrows = (int)min((long long)TILE, A.n - r0);
+  const int T = A.T;
+  load_theta(a, A.theta + (long long)m * a.P, sm);
+  int *rows = reinterpret_cast<int *>(sm + a.o_rows);
+  for (int b = threadIdx.x; b < TILE; b += NT) rows[b] = (int)(b < nrows ? b : 0);
+  Src<float> src;
+  src.X = A.X + ((long long)m * A.n + r0) * (A.m2m ? (long long)T * a.D : a.D);
+  src.row_stride = A.m2m ? (long long)T * a.D : a.D;
+  src.x_step = A.m2m ? a.D : 0;
+  __syncthreads();
+  make_mask(a, src, rows, nrows, T, A.use_mask, A.mask_value, sm + a.o_mask);
+  __syncthreads();
+  tile_forward(a, sm, src, nrows, T, nullptr);
+  const float *logit = sm + a.o_logit;
+  if (A.m2m) {
+    float *o = A.out + ((long long)m * A.n + r0) * T;
+    for (int i = threadIdx.x; i < nrows * T; i += NT) o[i] = logit[i];
+  } else {
+    float *o = A.out + (long long)m * A.n + r0;
+    for (int b = threadIdx.x; b < nrows; b += NT) o[b] = logit[b * T + T - 1];
+  }
+}
+
+struct VgArgs {
+  Lay a;
+  const float *theta;
+  const double *X;
+  long long n;
+  int T, transform, negate;
+  float *val, *ws;
+  double *grad;
+};
+
+__global__ void __launch_bounds__(NT) lstm_value_grad_kernel(VgArgs A) {
+  extern __shared__ float sm[];
+  const Lay &a = A.a;
+  const int m = blockIdx.y;
+  const long long r0 = (long long)blockIdx.x * TILE;
+  const int nrows = (int)min((long long)TILE, A.n - r0);
+  const int T = A.T;
+  float *ws = A.ws + ((long long)m * gridDim.x + blockIdx.x) * a.ws_floats;
+  load_theta(a, A.theta + (long long)m * a.P, sm);
+  int *rows = reinterpret_cast<int *>(sm + a.o_rows);
+  for (int b = threadIdx.x; b < TILE; b += NT) rows[b] = (int)(b < nrows ? b : 0);
+  Src<double> src;
+  src.X = A.X + ((long long)m * A.n + r0) * a.D;
+  src.row_stride = a.D;
+  src.x_step = 0;
+  __syncthreads();
+  make_mask(a, src, rows, nrows, T, 0, 0.f, sm + a.o_mask);
+  __syncthreads();
+  tile_forward(a, sm, src, nrows, T, ws);
+  // value and d value / d f at the last step
+  const float *logit = sm + a.o_logit;
+  float *dlogit = sm + a.o_dlogit;
+  for (int i = threadIdx.x; i < nrows * T; i += NT) {
+    const int b = i / T, t = i % T;
+    if (t != T - 1) { dlogit[i] = 0.f; continue; }
+    const float f = logit[i], s = A.negate ? -1.f : 1.f, u = s * f;
+    float v, dv;
+    if (A.transform == BORE_T_SIGMOID) { v = sig(u); dv = s * (v * (1.f - v)); }
+    else if (A.transform == BORE_T_EXP) { v = expf(u); dv = s * v; }
+    else { v = u; dv = s; }
+    A.val[(long long)m * A.n + r0 + b] = v;
+    dlogit[i] = dv;
+  }
+  __syncthreads();
+  tile_backward(a, sm, src, nrows, T, ws, nullptr, true);
+  const float *dx = sm + a.o_dx;
+  double *g = A.grad + ((long long)m * A.n + r0) * a.D;
+  for (int i = threadIdx.x; i < nrows * a.D; i += NT) g[i] = (double)dx[i];
+}
+
+struct FitArgsL {
+  Lay a;
+  float *theta, *am, *av;
+  long long *at;
+  const float *X, *Y;
+  const int *perm;
+  float *epoch_loss, *ws, *gacc;
+  long long N;
+  int T, epochs, B;
+  float mask_value, lr, beta1, beta2, eps;
+};
+
+__global__ void __launch_bounds__(NT) lstm_fit_kernel(FitArgsL A) {
+  extern __shared__ float sm[];
+  const Lay &a = A.a;
+  const int m = blockIdx.x, T = A.T;
+  const long long N = A.N;
+  float *th_g = A.theta + (long long)m * a.P, *m_g = A.am + (long long)m * a.P, *v_g = A.av + (long long)m * a.P;
+  float *ws = A.ws + (long long)m * a.ws_floats, *gacc = A.gacc + (long long)m * a.P;
+  load_theta(a, th_g, sm);
+  const long long t0 = A.at[m];
+  double b1p = pow((double)A.beta1, (double)t0), b2p = pow((double)A.beta2, (double)t0);
+  const float omb1 = 1.f - A.beta1, omb2 = 1.f - A.beta2;
+  Src<float> src;
+  src.X = A.X + (long long)m * N * T * a.D;
+  src.row_stride = (long long)T * a.D;
+  src.x_step = a.D;
+  const float *Y = A.Y + (long long)m * N * T;
+  int *rows = reinterpret_cast<int *>(sm + a.o_rows);
+  long long steps = 0;
+  for (int e = 0; e < A.epochs; ++e) {
+    double eloss = 0.0;
+    const int *pe = A.perm + ((long long)m * A.epochs + e) * N;
+    for (long long s0 = 0; s0 < N; s0 += A.B) {
+      const int nrows = (int)min((long long)A.B, N - s0);
+      __syncthreads();
+      for (int b = threadIdx.x; b < TILE; b += NT) rows[b] = b < nrows ? pe[s0 + b] : 0;
+      __syncthreads();
+      make_mask(a, src, rows, nrows, T, 1, A.mask_value, sm + a.o_mask);
+      __syncthreads();
+      tile_forward(a, sm, src, nrows, T, ws);
+      const float bce = tile_bce(a, sm, Y, T, nrows, T, 1.f / (float)(nrows * T));
+      tile_backward(a, sm, src, nrows, T, ws, gacc, false);
+      // Adam (ResourceApplyAdam), the l2 penalties of the loss on the weights before the update
+      ++steps;
+      b1p *= (double)A.beta1;
+      b2p *= (double)A.beta2;
+      const float alpha = A.lr * sqrtf(1.f - (float)b2p) / (1.f - (float)b1p);
+      float pen = 0.f;
+      for (int p = threadIdx.x; p < a.P; p += NT) {
+        const int li = lds_of(a, p);
+        const float w = sm[li], f = l2_of(a, p);
+        pen = fmaf(f * w, w, pen);
+        const float g = gacc[p] + 2.f * f * w;
+        float mm = m_g[p], vv = v_g[p];
+        mm += (g - mm) * omb1;
+        vv += (g * g - vv) * omb2;
+        sm[li] = w - (mm * alpha) / (sqrtf(vv) + A.eps);
+        m_g[p] = mm;
+        v_g[p] = vv;
+        gacc[p] = 0.f;
+      }
+      const float penalty = block_sum(pen, sm + a.o_red);
+      eloss += (double)(bce / (float)(nrows * T) + penalty) * nrows;
+    }
+    if (A.epoch_loss && threadIdx.x == 0) A.epoch_loss[(long long)m * A.epochs + e] = (float)(eloss / (double)N);
+  }
+  __syncthreads();
+  for (int p = threadIdx.x; p < a.P; p += NT) th_g[p] = sm[lds_of(a, p)];
+  if (threadIdx.x == 0) A.at[m] = t0 + steps;
+}
+
+struct EvalArgsL {
+  Lay a;
+  const float *theta, *X, *Y;
+  long long N;
+  int T;
+  float mask_value;
+  float *loss, *acc;
+};
+
+__global__ void __launch_bounds__(NT) lstm_evaluate_kernel(EvalArgsL A) {
+  extern __shared__ float sm[];
+  const Lay &a = A.a;
+  const int m = blockIdx.x, T = A.T;
+  const long long N = A.N;
+  load_theta(a, A.theta + (long long)m * a.P, sm);
+  Src<float> src;
+  src.X = A.X + (long long)m * N * T * a.D;
+  src.row_stride = (long long)T * a.D;
+  src.x_step = a.D;
+  const float *Y = A.Y + (long long)m * N * T;
+  int *rows = reinterpret_cast<int *>(sm + a.o_rows);
+  double tot = 0.0, hit = 0.0, live_n = 0.0;
+  for (long long s0 = 0; s0 < N; s0 += TILE) {
+    const int nrows = (int)min((long long)TILE, N - s0);
+    __syncthreads();
+    for (int b = threadIdx.x; b < TILE; b += NT) rows[b] = (int)(s0 + (b < nrows ? b : 0));
+    __syncthreads();
+    make_mask(a, src, rows, nrows, T, 1, A.mask_value, sm + a.o_mask);
+    __syncthreads();
+    tile_forward(a, sm, src, nrows, T, nullptr);
+    const float bce = tile_bce(a, sm, Y, T, nrows, T, 0.f);
+    // binary_accuracy on the model output (the logit) at 0.5, weighted by the mask
+    const float *mask = sm + a.o_mask, *logit = sm + a.o_logit;
+    float h = 0.f, n = 0.f;
+    for (int it = threadIdx.x; it < nrows * T; it += NT) {
+      const int b = it / T, t = it % T;
+      const float y = Y[(long long)rows[b] * T + t];
+      const bool live = mask[it] != 0.f;
+      h += live && ((logit[it] > 0.5f) == (y > 0.5f)) ? 1.f : 0.f;
+      n += live ? 1.f : 0.f;
+    }
+    const float hs = block_sum(h, sm + a.o_red), ns = block_sum(n, sm + a.o_red);
+    tot += (double)bce;
+    hit += (double)hs;
+    live_n += (double)ns;
+  }
+  float pen = 0.f;
+  for (int p = threadIdx.x; p < a.P; p += NT) {
+    const float w = sm[lds_of(a, p)];
+    pen = fmaf(l2_of(a, p) * w, w, pen);
+  }
+  const float penalty = block_sum(pen, sm + a.o_red);
+  if (threadIdx.x == 0) {
+    A.loss[m] = (float)(tot / ((double)N * T)) + penalty;
+    A.acc[m] = live_n > 0 ? (float)(hit / live_n) : 0.f;
+  }
+}
+
+}  // namespace bore_lstm
+
+// --------------------------------------------------------------------------------------------------
+// C ABI
+// --------------------------------------------------------------------------------------------------
+using namespace bore_lstm;
+
+extern "C" int64_t bore_lstm_param_count(const bore_lstm_desc *desc) {
+  // (a property of the network: counted for any valid descriptor, also one the kernels do not take)
+  if (!desc) return fail(BORE_E_INVALID, "lstm: null descriptor");
+  if (desc->input_dim < 1 || desc->n_layers < 1 || desc->units < 1 || desc->output_dim < 1)
+    return fail(BORE_E_INVALID, "lstm: input_dim, n_layers, units and output_dim must be positive (got %d, %d, %d, %d)",
+                desc->input_dim, desc->n_layers, desc->units, desc->output_dim);
+  int64_t P = 0;
+  for (int l = 0; l < desc->n_layers; ++l)
+    P += (int64_t)((l ? desc->units : desc->input_dim) + desc->units + 1) * 4 * desc->units;
+  return P + (int64_t)(desc->units + 1) * desc->output_dim;
+}
+
+static int lstm_common(const bore_lstm_desc *desc, int n_models, int T, Lay *a, const char *what) {
+  if (n_models < 1) return fail(BORE_E_INVALID, "%s: n_models must be >= 1 (got %d)", what, n_models);
+  if (T < 1) return fail(BORE_E_INVALID, "%s: need at least one step (got %d)", what, T);
+  return make_lay(desc, T, a);
+}
+
+extern "C" int bore_lstm_forward(const bore_lstm_desc *desc, int n_models, const float *theta, const float *X,
+                                 int64_t n_rows, int T, int many_to_many, float mask_value, float *out,
+                                 void *stream) {
+  FwdArgs A;
+  int rc = lstm_common(desc, n_models, T, &A.a, "lstm_forward");
+  if (rc) return rc;
+  if (!theta || !X || !out) return fail(BORE_E_INVALID, "lstm_forward: null pointer");
+  if (n_rows < 0) return fail(BORE_E_INVALID, "lstm_forward: n_rows < 0");
+  if (n_rows == 0) return 0;
+  A.theta = theta; A.X = X; A.n = n_rows; A.T = T; A.m2m = many_to_many ? 1 : 0;
+  A.use_mask = A.m2m; A.mask_value = mask_value; A.out = out;
+  const size_t bytes = (size_t)A.a.lds_floats * 4;
+  rc = allow_lds(lstm_forward_kernel, bytes);
+  if (rc) return rc;
+  const long long tiles = (n_rows + TILE - 1) / TILE;
+  if (tiles > 0x7fffffffLL) return fail(BORE_E_UNSUPPORTED, "lstm_forward: too many rows");
+  hipLaunchKernelGGL(lstm_forward_kernel, dim3((unsigned)tiles, n_models), dim3(NT), bytes, (hipStream_t)stream, A);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+extern "C" int bore_lstm_value_and_input_grad(const bore_lstm_desc *desc, int n_models, const float *theta,
+                                              const double *X, int64_t n_rows, int num_steps, int transform,
+                                              int negate, float *val, double *grad, void *stream) {
+  VgArgs A;
+  int rc = lstm_common(desc, n_models, num_steps, &A.a, "lstm_value_and_input_grad");
+  if (rc) return rc;
+  if (!theta || !X || !val || !grad) return fail(BORE_E_INVALID, "lstm_value_and_input_grad: null pointer");
+  if (transform < BORE_T_IDENTITY || transform > BORE_T_EXP)
+    return fail(BORE_E_INVALID, "lstm_value_and_input_grad: unknown transform %d", transform);
+  if (n_rows < 0) return fail(BORE_E_INVALID, "lstm_value_and_input_grad: n_rows < 0");
+  if (n_rows == 0) return 0;
+  const long long tiles = (n_rows + TILE - 1) / TILE;
+  if (tiles > 0x7fffffffLL) return fail(BORE_E_UNSUPPORTED, "lstm_value_and_input_grad: too many rows");
+  A.theta = theta; A.X = X; A.n = n_rows; A.T = num_steps; A.transform = transform; A.negate = negate ? 1 : 0;
+  A.val = val; A.grad = grad;
+  const size_t bytes = (size_t)A.a.lds_floats * 4;
+  rc = allow_lds(lstm_value_grad_kernel, bytes);
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipMallocAsync((void **)&A.ws, (size_t)n_models * tiles * A.a.ws_floats * 4, st));
+  hipLaunchKernelGGL(lstm_value_grad_kernel, dim3((unsigned)tiles, n_models), dim3(NT), bytes, st, A);
+  const hipError_t e = hipGetLastError();
+  (void)hipFreeAsync(A.ws, st);
+  if (e != hipSuccess) return fail(BORE_E_HIP, "lstm_value_grad_kernel: %s", hipGetErrorString(e));
+  return 0;
+}
+
+extern "C" int bore_lstm_fit(const bore_lstm_desc *desc, int n_models, float *theta, float *adam_m, float *adam_v,
+                             int64_t *adam_t, const float *X, const float *y, int64_t N, int T, float mask_value,
+                             int epochs, int batch_size, const int32_t *perm, const bore_adam_cfg *adam,
+                             float *epoch_loss, void *stream) {
+  FitArgsL A;
+  int rc = lstm_common(desc, n_models, T, &A.a, "lstm_fit");
+  if (rc) return rc;
+  if (!theta || !adam_m || !adam_v || !adam_t || !X || !y || !adam)
+    return fail(BORE_E_INVALID, "lstm_fit: null pointer");
+  if (N < 1 || epochs < 0) return fail(BORE_E_INVALID, "lstm_fit: N must be >= 1 and epochs >= 0");
+  if (batch_size < 1) return fail(BORE_E_INVALID, "lstm_fit: batch_size must be >= 1");
+  if (batch_size > TILE)
+    return fail(BORE_E_UNSUPPORTED, "lstm_fit: batch_size %d > %d (one tile of sequences per Adam step)",
+                batch_size, TILE);
+  if (epochs == 0) return 0;
+  if (!perm) return fail(BORE_E_INVALID, "lstm_fit: explicit per-epoch permutations are required");
+  if (N > 0x7fffffffLL) return fail(BORE_E_UNSUPPORTED, "lstm_fit: N > 2^31 - 1");
+  A.theta = theta; A.am = adam_m; A.av = adam_v; A.at = (long long *)adam_t; A.X = X; A.Y = y; A.perm = perm;
+  A.epoch_loss = epoch_loss; A.N = N; A.T = T; A.epochs = epochs; A.B = batch_size; A.mask_value = mask_value;
+  A.lr = adam->lr; A.beta1 = adam->beta1; A.beta2 = adam->beta2; A.eps = adam->eps;
+  const size_t bytes = (size_t)A.a.lds_floats * 4;
+  rc = allow_lds(lstm_fit_kernel, bytes);
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t n_ws = (size_t)n_models * A.a.ws_floats, n_g = (size_t)n_models * A.a.P;
+  float *buf = nullptr;
+  HIP_TRY(hipMallocAsync((void **)&buf, (n_ws + n_g) * 4, st));
+  A.ws = buf;
+  A.gacc = buf + n_ws;
+  hipError_t e = hipMemsetAsync(A.gacc, 0, n_g * 4, st);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(lstm_fit_kernel, dim3(n_models), dim3(NT), bytes, st, A);
+    e = hipGetLastError();
+  }
+  (void)hipFreeAsync(buf, st);
+  if (e != hipSuccess) return fail(BORE_E_HIP, "lstm_fit: %s", hipGetErrorString(e));
+  return 0;
+}
+
+extern "C" int bore_lstm_evaluate(const bore_lstm_desc *desc, int n_models, const float *theta, const float *X,
+                                  const float *y, int64_t N, int T, float mask_value, float *loss, float *acc,
+                                  void *stream) {
+  EvalArgsL A;
+  int rc = lstm_common(desc, n_models, T, &A.a, "lstm_evaluate");
+  if (rc) return rc;
+  if (!theta || !X || !y || !loss || !acc) return fail(BORE_E_INVALID, "lstm_evaluate: null pointer");
+  if (N < 1) return fail(BORE_E_INVALID, "lstm_evaluate: N < 1");
+  A.theta = theta; A.X = X; A.Y = y; A.N = N; A.T = T; A.mask_value = mask_value; A.loss = loss; A.acc = acc;
+  const size_t bytes = (size_t)A.a.lds_floats * 4;
+  rc = allow_lds(lstm_evaluate_kernel, bytes);
+  if (rc) return rc;
+  hipLaunchKernelGGL(lstm_evaluate_kernel, dim3(n_models), dim3(NT), bytes, (hipStream_t)stream, A);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}

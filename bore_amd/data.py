@@ -50,3 +50,113 @@ def classification_labels(y, gamma):
     """z = y < np.quantile(y, gamma)   (bore/data.py:33-34)."""
     y = np.asarray(y)
     return np.less(y, np.quantile(y, q=gamma))
+
+
+class MultiFidelityRecord:
+    """Observations of a Hyperband run, keyed by configuration and budget (behaviour of
+    bore/data.py:51-261).  A rung is a budget; rungs are numbered by increasing budget.  Labels at a rung
+    are ``y <= quantile(y_rung, gamma)`` -- note ``<=``, where ``Record`` uses ``<``.  Recording the same
+    ``(x, b)`` twice replaces the value in the per-configuration table but appends to the rung's target
+    list again (as the reference does).  Configurations keep their insertion order."""
+
+    def __init__(self, gamma=None):
+        self._data = {}          # key(x) -> {budget: y}
+        self._targets = {}       # budget -> [y, ...] in arrival order
+        self.gamma = gamma
+
+    @staticmethod
+    def compute_key(x):
+        return tuple(x.tolist())
+
+    def append(self, x, y, b):
+        self._data.setdefault(self.compute_key(x), {})[b] = y
+        self._targets.setdefault(b, []).append(y)
+
+    def num_rungs(self):
+        return len(self._targets)
+
+    def budgets(self, reverse=False):
+        return sorted(self._targets, reverse=reverse)
+
+    def budget(self, t):
+        return self.budgets()[t]
+
+    def _rung_size_from_budget(self, b):
+        return len(self._targets[b])
+
+    def highest_rung(self, min_size=1):
+        """The highest rung with at least ``min_size`` observations, or None."""
+        best = None
+        for t, b in enumerate(self.budgets()):
+            if self._rung_size_from_budget(b) >= min_size:
+                best = t
+        return best
+
+    def rung_sizes(self):
+        return [self._rung_size_from_budget(b) for b in self.budgets()]
+
+    def rung_size(self, t):
+        return self._rung_size_from_budget(self.budget(t))
+
+    def size(self):
+        return sum(self.rung_sizes())
+
+    def load_feature_matrix(self):
+        return np.vstack(self._data)
+
+    def num_features(self):
+        return len(self._data)
+
+    def _targets_from_budget(self, b):
+        return self._targets[b]
+
+    def targets(self, t):
+        return self._targets_from_budget(self.budget(t))
+
+    def _threshold_from_budget(self, b):
+        return np.quantile(self._targets_from_budget(b), q=self.gamma)
+
+    def threshold(self, t):
+        return self._threshold_from_budget(self.budget(t))
+
+    def thresholds(self):
+        return [self._threshold_from_budget(b) for b in self.budgets()]
+
+    def _binary_labels_from_budget(self, b):
+        return np.less_equal(self._targets_from_budget(b), self._threshold_from_budget(b))
+
+    def binary_labels(self, t):
+        return self._binary_labels_from_budget(self.budget(t))
+
+    def sequences_dict(self, pad_value=-1., binary=True, return_indices=False):
+        """key -> list over the rungs of the label (binary) or value, ``pad_value`` where the configuration
+        has no observation; with ``return_indices`` also key -> list of "observed" flags."""
+        assert not binary or self.gamma is not None, \
+            "Must instantiate with `gamma` specified for binary labels!"
+        seqs = {k: [] for k in self._data}
+        seen = {k: [] for k in self._data}
+        for b in self.budgets():
+            tau = self._threshold_from_budget(b)
+            for k, dct in self._data.items():
+                have = b in dct
+                if have:
+                    seqs[k].append(int(dct[b] <= tau) if binary else dct[b])
+                else:
+                    seqs[k].append(pad_value)
+                seen[k].append(have)
+        return (seqs, seen) if return_indices else seqs
+
+    def sequences(self, pad_value=-1., binary=True):
+        """(inputs [n, T, D] float64 with ``pad_value`` rows at the rungs a configuration lacks,
+        targets [n, T, 1])."""
+        seqs, seen = self.sequences_dict(pad_value=pad_value, binary=binary, return_indices=True)
+        inputs, targets = [], []
+        for k, ys in seqs.items():
+            seq = np.full((len(ys), len(k)), pad_value, dtype="float64")
+            seq[seen[k]] = np.array(k)
+            inputs.append(seq)
+            targets.append(np.expand_dims(ys, axis=-1))
+        return np.stack(inputs, axis=0), np.stack(targets, axis=0)
+
+    def is_duplicate(self, x, rtol=1e-5, atol=1e-8):
+        return any(np.allclose(np.array(k), x, rtol=rtol, atol=atol) for k in self._data)

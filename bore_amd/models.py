@@ -367,7 +367,7 @@ class DenseSequential(Sequential):
 
 class Model(Sequential):
     """Stand-in for ``tensorflow.keras.Model`` restricted to a Dense stack (``layers=[...]``);
-    the functional API (used only by the out-of-scope LSTM factory) is not provided."""
+    the functional API is not provided (the LSTM factory below does not need it)."""
 
 
 class MaximizableModel(MaximizableMixin, Model):
@@ -394,6 +394,339 @@ class BatchMaximizableDenseSequential(BatchMaximizableMixin, DenseSequential):
     pass
 
 
+class LSTMCell:
+    """``tensorflow.keras.layers.LSTMCell(units, activation="tanh", kernel_regularizer=None,
+    bias_regularizer=None)``: a record of the arguments StackedRecurrentFactory passes.  The other
+    Keras defaults hold and are not settable here: recurrent activation the logistic sigmoid (TF 2.x),
+    glorot_uniform kernel, orthogonal recurrent kernel, zero bias with the forget block at one."""
+
+    def __init__(self, units, activation="tanh", kernel_regularizer=None, bias_regularizer=None, **kwargs):
+        from .layers import ACTIVATIONS, _reg_factor
+        if kwargs:
+            raise NotImplementedError(f"LSTMCell arguments {sorted(kwargs)} are not available on the HIP path")
+        if callable(activation) and hasattr(activation, "__name__"):
+            activation = activation.__name__
+        activation = "linear" if activation is None else activation
+        if activation not in ACTIVATIONS:
+            raise ValueError(f"activation {activation!r} is not supported on the HIP path (supported: {ACTIVATIONS})")
+        self.units = int(units)
+        self.activation = activation
+        self.l2_kernel = _reg_factor(kernel_regularizer)
+        self.l2_bias = _reg_factor(bias_regularizer)
+
+
+def _orthogonal(rs, rows, cols):
+    """Keras ``Orthogonal(gain=1)`` for a (rows, cols) kernel: QR of a standard normal draw of the taller
+    shape, columns signed by diag(R), transposed back when wide."""
+    a = rs.normal(0.0, 1.0, size=(max(rows, cols), min(rows, cols)))
+    q, r = np.linalg.qr(a)
+    q = q * np.sign(np.diag(r))
+    return (q.T if rows < cols else q).astype(np.float32)
+
+
+class StackedRecurrentFactory:
+    """bore/models.py:48-104 on MI355X.  ``num_layers`` LSTM cells and a Dense head whose parameters the
+    factory owns on the device (``theta``, one packed fp32 vector in get_weights() order); the
+    networks it builds read the LIVE parameters, so training the many-to-many network changes every
+    one-to-one network, also those built earlier.  ``seed`` (an extension) seeds the initialisation
+    and the shuffles."""
+
+    def __init__(self, input_dim, output_dim, num_layers=2, num_units=32, layer_kws={}, final_layer_kws={},
+                 seed=None):
+        self.input_dim = input_dim
+        assert "return_sequences" not in layer_kws
+        assert "activation" not in final_layer_kws
+        self.cells = [LSTMCell(num_units, **layer_kws) for _ in range(num_layers)]
+        self.final_layer = Dense(output_dim, **final_layer_kws)
+        self.output_dim = int(output_dim)
+        self.num_layers, self.num_units = int(num_layers), int(num_units)
+        self._rs = np.random.RandomState(seed)
+        self._shuffle_seed = int(self._rs.randint(0, 2**31 - 1)) if seed is None else int(seed)
+        cell = self.cells[0] if self.cells else LSTMCell(num_units)
+        self._desc = _lib.make_lstm_desc(
+            input_dim, num_layers, num_units, cell.activation,
+            [c.l2_kernel for c in self.cells] + [self.final_layer.l2_kernel],
+            [c.l2_bias for c in self.cells] + [self.final_layer.l2_bias], output_dim=output_dim)
+        self.theta = None
+
+    def count_params(self):
+        D, H, n = int(self.input_dim), self.num_units, 0
+        for l in range(self.num_layers):
+            n += ((H if l else D) + H + 1) * 4 * H
+        return n + (H + 1) * self.output_dim
+
+    def _initial_weights(self):
+        D, H = int(self.input_dim), self.num_units
+        ws = []
+        for l in range(self.num_layers):
+            fan_in = H if l else D
+            limit = np.sqrt(6.0 / (fan_in + 4 * H))
+            ws.append(self._rs.uniform(-limit, limit, size=(fan_in, 4 * H)).astype(np.float32))
+            ws.append(_orthogonal(self._rs, H, 4 * H))
+            b = np.zeros(4 * H, dtype=np.float32)
+            b[H:2 * H] = 1.0                      # unit_forget_bias=True
+            ws.append(b)
+        limit = np.sqrt(6.0 / (H + self.output_dim))
+        ws.append(self._rs.uniform(-limit, limit, size=(H, self.output_dim)).astype(np.float32))
+        ws.append(np.zeros(self.output_dim, dtype=np.float32))
+        return ws
+
+    def _ensure_built(self, x=None):
+        if x is not None and np.shape(x)[-1] != self.input_dim:
+            raise ValueError(f"expected input dimension {self.input_dim}, got {np.shape(x)[-1]}")
+        if self.theta is None:
+            dev = _lib.require_gpu()
+            flat = np.concatenate([w.reshape(-1) for w in self._initial_weights()])
+            assert flat.size == self.count_params()
+            self.theta = torch.from_numpy(flat).to(dev).reshape(1, -1).contiguous()
+
+    def get_weights(self):
+        self._ensure_built()
+        flat = self.theta[0].cpu().numpy()
+        D, H, out, off = int(self.input_dim), self.num_units, [], 0
+        shapes = []
+        for l in range(self.num_layers):
+            shapes += [((H if l else D), 4 * H), (H, 4 * H), (4 * H,)]
+        shapes += [(H, self.output_dim), (self.output_dim,)]
+        for shp in shapes:
+            n = int(np.prod(shp))
+            out.append(flat[off:off + n].reshape(shp).copy())
+            off += n
+        return out
+
+    def set_weights(self, weights):
+        cur = self.get_weights()
+        if len(weights) != len(cur) or any(np.shape(a) != b.shape for a, b in zip(weights, cur)):
+            raise ValueError("weight shapes do not match the model")
+        flat = np.concatenate([np.asarray(w, dtype=np.float32).reshape(-1) for w in weights])
+        self.theta.copy_(torch.from_numpy(flat).reshape(1, -1))
+
+    def build_many_to_many(self, mask_value=1e+9):
+        """Masking -> RNN(cell, return_sequences=True) x L -> TimeDistributed(Dense): [n, T, D] -> [n, T, 1]
+        logits, for fit / evaluate."""
+        return ManyToManyNetwork(self, mask_value)
+
+    def build_one_to_one(self, num_steps, transform=None):
+        """RepeatVector(num_steps) -> RNN x L (the last without sequences) -> Dense: [n, D] -> [n, 1], a
+        maximizable network (predict / maxima / argmax)."""
+        return MaximizableOneToOneNetwork(transform, self, num_steps)
+
+
+class _RecurrentNetwork:
+    """What both networks share: the factory's live parameters."""
+
+    def __init__(self, factory):
+        self.factory = factory
+
+    @property
+    def theta(self):
+        self.factory._ensure_built()
+        return self.factory.theta
+
+    @property
+    def _desc(self):
+        return self.factory._desc
+
+    @property
+    def _input_dim(self):
+        return self.factory.input_dim
+
+    def _ensure_built(self, x=None):
+        self.factory._ensure_built(x)
+
+    def get_weights(self):
+        return self.factory.get_weights()
+
+    def set_weights(self, weights):
+        self.factory.set_weights(weights)
+
+    def count_params(self):
+        return self.factory.count_params()
+
+    def summary(self, print_fn=print):
+        f = self.factory
+        print_fn(f'Model: "{self.name}"')
+        for i, c in enumerate(f.cells):
+            n = ((f.num_units if i else f.input_dim) + f.num_units + 1) * 4 * f.num_units
+            print_fn(f" rnn_{i} (RNN/LSTMCell)  units {c.units}  activation {c.activation}  params {n}")
+        print_fn(f" dense (Dense)  output {f.output_dim}  params {(f.num_units + 1) * f.output_dim}")
+        print_fn(f"Total params: {f.count_params()}")
+
+
+class ManyToManyNetwork(_RecurrentNetwork):
+    """The training network of the factory (bore/models.py:64-82).  The Adam slots and counter belong to
+    this network (its compiled optimizer) and persist across ``fit`` calls."""
+
+    name = "many_to_many"
+
+    def __init__(self, factory, mask_value=1e9):
+        super().__init__(factory)
+        self.mask_value = float(mask_value)
+        self._optimizer, self._loss, self._metrics, self._compiled = Adam(), None, [], False
+        self.adam_m = self.adam_v = self.adam_t = None
+        self._epochs_seen = 0
+
+    def compile(self, optimizer="adam", loss=None, metrics=None, **kwargs):
+        self._optimizer = resolve_optimizer(optimizer)
+        self._loss = resolve_loss(loss)
+        self._metrics = list(metrics or [])
+        for m in self._metrics:
+            if m not in ("accuracy", "acc", "binary_accuracy"):
+                raise NotImplementedError(f"metric {m!r} is not available on the HIP path")
+        if self._loss is not None and not self._loss.from_logits:
+            raise NotImplementedError("the recurrent classifier's head is linear: compile with "
+                                      "BinaryCrossentropy(from_logits=True)")
+        self._compiled = True
+
+    def _check_loss(self):
+        if not self._compiled or self._loss is None:
+            raise RuntimeError("compile(optimizer=..., loss=...) the model before fit/evaluate")
+
+    def _data(self, x, y=None):
+        x = np.asarray(x, dtype=np.float32)
+        if x.ndim != 3:
+            raise ValueError(f"expected input sequences [n, T, D], got shape {x.shape}")
+        self._ensure_built(x)
+        n, T = x.shape[:2]
+        if T > _lib.LSTM_MAX_STEPS:
+            raise _lib.UnsupportedError(f"{T} steps > {_lib.LSTM_MAX_STEPS} (BORE_LSTM_MAX_STEPS)")
+        dev = self.theta.device
+        X = torch.from_numpy(np.ascontiguousarray(x)).to(dev).reshape(1, n, T, -1)
+        if y is None:
+            return X, None
+        yv = np.asarray(y, dtype=np.float32).reshape(n, T)
+        return X, torch.from_numpy(np.ascontiguousarray(yv)).to(dev).reshape(1, n, T)
+
+    def _perm(self, epochs, N, shuffle, perm):
+        dev = self.theta.device
+        if perm is None and not shuffle:
+            perm = np.tile(np.arange(N, dtype=np.int32), (epochs, 1))
+        if perm is not None:
+            perm = np.asarray(perm)
+            if perm.shape != (epochs, N) or not np.array_equal(np.sort(perm, axis=1),
+                                                               np.tile(np.arange(N), (epochs, 1))):
+                raise ValueError("perm must hold one permutation of range(N) per epoch")
+            return torch.from_numpy(np.ascontiguousarray(perm, dtype=np.int32)).to(dev).reshape(1, epochs, N)
+        try:      # the shuffle stream of the Dense fit, drawn on the device
+            return ops.shuffle_perm(self.factory._shuffle_seed, 1, epochs, N, epoch0=self._epochs_seen, device=dev)
+        except _lib.UnsupportedError:          # (its host statement: the same permutations)
+            p = _shuffle.permutations(self.factory._shuffle_seed, 1, epochs, N, epoch0=self._epochs_seen)
+            return torch.from_numpy(p).to(dev)
+
+    def fit(self, x, y, epochs=1, batch_size=None, callbacks=None, verbose=False, shuffle=True, perm=None,
+            **kwargs):
+        """Keras ``fit`` over sequences (``perm`` (epochs, N): explicit shuffles, an extension).  Returns a
+        ``History``; one launch for all epochs, or one per epoch when callbacks are given."""
+        self._check_loss()
+        X, y = self._data(x, y)
+        N = X.shape[1]
+        batch_size = 32 if batch_size is None else int(batch_size)
+        if batch_size < 1:
+            raise ValueError(f"batch_size must be positive, got {batch_size}")
+        epochs = int(epochs)
+        if self.adam_m is None:
+            self.adam_m = torch.zeros_like(self.theta)
+            self.adam_v = torch.zeros_like(self.theta)
+            self.adam_t = torch.zeros(1, dtype=torch.int64, device=self.theta.device)
+        P = self._perm(epochs, N, shuffle, perm)
+        o = self._optimizer
+
+        def launch(e0, n):
+            loss = ops.lstm_fit(self._desc, self.theta, self.adam_m, self.adam_v, self.adam_t, X, y, n, batch_size,
+                                P[:, e0:e0 + n].contiguous(), mask_value=self.mask_value, lr=o.learning_rate,
+                                beta1=o.beta_1, beta2=o.beta_2, eps=o.epsilon)
+            self._epochs_seen += n
+            return loss
+
+        callbacks = list(callbacks or [])
+        if not callbacks:
+            loss = launch(0, epochs)
+            if verbose:
+                for e, v in enumerate(loss[0].cpu().numpy()):
+                    print(f"Epoch {e + 1}/{epochs} - loss: {float(v):.4f}")
+            return History(lambda: loss[0].cpu().numpy())
+
+        def call(name, *args):
+            for cb in callbacks:
+                fn = getattr(cb, name, None)
+                if fn is not None:
+                    fn(*args)
+
+        self.stop_training = False
+        call("set_model", self)
+        call("on_train_begin", {})
+        losses = []
+        for e in range(epochs):
+            call("on_epoch_begin", e, {})
+            losses.append(float(launch(e, 1)[0].cpu().numpy()[0]))
+            call("on_epoch_end", e, {"loss": losses[-1]})
+            if self.stop_training:
+                break
+        call("on_train_end", {})
+        return History(np.asarray(losses, dtype=np.float32))
+
+    def evaluate(self, x, y, batch_size=None, verbose=False, **kwargs):
+        """[loss, accuracy] (loss alone without metrics) under the masking rules of bore_lstm_evaluate."""
+        self._check_loss()
+        X, y = self._data(x, y)
+        loss, acc = ops.lstm_evaluate(self._desc, self.theta, X, y, mask_value=self.mask_value)
+        if self._metrics:
+            return [float(loss[0]), float(acc[0])]
+        return float(loss[0])
+
+    def predict(self, x, batch_size=None, verbose=0, **kwargs):
+        """[n, T, D] -> (n, T, 1) float32 logits."""
+        X, _ = self._data(x)
+        out = ops.lstm_forward(self._desc, self.theta, X, mask_value=self.mask_value)
+        return out[0].cpu().numpy()[..., None]
+
+    def __call__(self, x, training=False):
+        return self.predict(x)
+
+    def get_optimizer_state(self):
+        """(m, v, t): Adam slots in get_weights() order + iteration counter."""
+        return (self.adam_m[0].cpu().numpy(), self.adam_v[0].cpu().numpy(), int(self.adam_t[0]))
+
+
+class OneToOneNetwork(_RecurrentNetwork):
+    """The prediction network of the factory (bore/models.py:84-104)."""
+
+    name = "one_to_one"
+
+    def __init__(self, factory, num_steps):
+        super().__init__(factory)
+        self.num_steps = int(num_steps)
+        if not 1 <= self.num_steps <= _lib.LSTM_MAX_STEPS:
+            raise _lib.UnsupportedError(f"num_steps {num_steps} outside 1..{_lib.LSTM_MAX_STEPS} "
+                                        "(BORE_LSTM_MAX_STEPS)")
+
+    def predict(self, x, batch_size=None, verbose=0, **kwargs):
+        """(n, D) -> (n, 1) float32."""
+        x = np.asarray(x, dtype=np.float32).reshape(-1, int(self.factory.input_dim))
+        self._ensure_built(x)
+        X = torch.from_numpy(np.ascontiguousarray(x)).to(self.theta.device).reshape(1, x.shape[0], -1)
+        out = ops.lstm_forward(self._desc, self.theta, X, num_steps=self.num_steps)
+        return out[0].cpu().numpy().reshape(-1, 1)
+
+    def __call__(self, x, training=False):
+        return self.predict(x)
+
+    def _value_and_input_grad(self, X, transform, negate):
+        """The hook base.convert takes for this network: X [1, R, D] f64 device."""
+        return ops.lstm_value_and_input_grad(self._desc, self.theta, X, self.num_steps, transform, negate)
+
+
+class MaximizableOneToOneNetwork(MaximizableMixin, OneToOneNetwork):
+    """``MaximizableSequential(transform=...)`` of the one-to-one form: screening through
+    bore_lstm_forward and argpartition on the host, the restarts as SciPy's L-BFGS-B state machines
+    advanced together with one bore_lstm_value_and_input_grad launch per round."""
+
+    restart_mode = "lockstep"
+    screen_mode = "host"
+
+
 __all__ = ["Sequential", "DenseSequential", "Model", "MaximizableModel", "MaximizableSequential",
            "MaximizableDenseSequential", "BatchMaximizableModel", "BatchMaximizableSequential",
-           "BatchMaximizableDenseSequential", "Dense", "BinaryCrossentropy", "Adam", "History"]
+           "BatchMaximizableDenseSequential", "Dense", "BinaryCrossentropy", "Adam", "History",
+           "LSTMCell", "StackedRecurrentFactory", "ManyToManyNetwork", "OneToOneNetwork",
+           "MaximizableOneToOneNetwork"]

@@ -381,3 +381,110 @@ def svgd_optimize(desc, theta, x_init, low=None, high=None, transform="identity"
                                              _lib.TRANSFORM[transform], _lib.ptr(x_init), n, lo_p, hi_p,
                                              C.byref(opts), _lib.ptr(out), _lib.stream_ptr()))
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# the multi-fidelity classifier (StackedRecurrentFactory): include/bore_hip.h bore_lstm_*
+# ------------------------------------------------------------------------------------------------
+def lstm_param_count(desc):
+    p = _lib.lib().bore_lstm_param_count(C.byref(desc))
+    if p < 0:
+        _lib.check(int(p))
+    return int(p)
+
+
+def lstm_forward(desc, theta, X, num_steps=None, mask_value=1e9, out=None):
+    """theta [L,P] f32.  X [L,N,T,D] f32 -> logits [L,N,T] (many-to-many, masked by ``mask_value``);
+    X [L,N,D] f32 with ``num_steps`` -> [L,N] (one-to-one: x repeated over the steps, last step)."""
+    L = theta.shape[0]
+    D = desc.input_dim
+    _chk(theta, torch.float32, (L, lstm_param_count(desc)), "theta")
+    m2m = X.dim() == 4
+    if m2m:
+        N, T = X.shape[1], X.shape[2]
+        _chk(X, torch.float32, (L, N, T, D), "X")
+        shape = (L, N, T)
+    else:
+        if num_steps is None:
+            raise ValueError("X [L,N,D]: the one-to-one form needs num_steps")
+        N, T = X.shape[1], int(num_steps)
+        _chk(X, torch.float32, (L, N, D), "X")
+        shape = (L, N)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=theta.device)
+    else:
+        _chk(out, torch.float32, shape, "out")
+    if N == 0:
+        return out
+    _lib.check(_lib.lib().bore_lstm_forward(C.byref(desc), L, _lib.ptr(theta), _lib.ptr(X), N, T, int(m2m),
+                                            float(mask_value), _lib.ptr(out), _lib.stream_ptr()))
+    return out
+
+
+def lstm_value_and_input_grad(desc, theta, X, num_steps, transform="identity", negate=True):
+    """theta [L,P] f32; X [L,R,D] f64 -> (val [L,R] f32, grad [L,R,D] f64) of T(+-f(x)), f the
+    one-to-one network over ``num_steps`` steps."""
+    L = theta.shape[0]
+    D = desc.input_dim
+    _chk(theta, torch.float32, (L, lstm_param_count(desc)), "theta")
+    if X.dim() != 3:
+        raise ValueError("X: expected [n_models, n_rows, D]")
+    R = X.shape[1]
+    _chk(X, torch.float64, (L, R, D), "X")
+    if transform not in _lib.TRANSFORM:
+        raise ValueError(f"unknown transform {transform!r}")
+    val = torch.empty((L, R), dtype=torch.float32, device=theta.device)
+    grad = torch.empty((L, R, D), dtype=torch.float64, device=theta.device)
+    if R == 0:
+        return val, grad
+    _lib.check(_lib.lib().bore_lstm_value_and_input_grad(
+        C.byref(desc), L, _lib.ptr(theta), _lib.ptr(X), R, int(num_steps), _lib.TRANSFORM[transform],
+        int(bool(negate)), _lib.ptr(val), _lib.ptr(grad), _lib.stream_ptr()))
+    return val, grad
+
+
+def lstm_fit(desc, theta, m, v, t, X, y, epochs, batch_size, perm, mask_value=1e9, lr=1e-3, beta1=0.9,
+             beta2=0.999, eps=1e-7, want_loss=True):
+    """In-place fit of L many-to-many networks over X [L,N,T,D] f32, y [L,N,T] f32 with explicit
+    per-epoch permutations perm [L,epochs,N] int32.  Returns epoch_loss [L,epochs] f32 (or None)."""
+    L = theta.shape[0]
+    D = desc.input_dim
+    P = lstm_param_count(desc)
+    _chk(theta, torch.float32, (L, P), "theta")
+    _chk(m, torch.float32, (L, P), "adam_m")
+    _chk(v, torch.float32, (L, P), "adam_v")
+    _chk(t, torch.int64, (L,), "adam_t")
+    if X.dim() != 4:
+        raise ValueError("X: expected [n_models, N, T, D]")
+    N, T = X.shape[1], X.shape[2]
+    _chk(X, torch.float32, (L, N, T, D), "X")
+    _chk(y, torch.float32, (L, N, T), "y")
+    epochs = int(epochs)
+    _chk(perm, torch.int32, (L, epochs, N), "perm")
+    # an out-of-range row index would read outside X: validate before launching
+    if epochs and N and (int(perm.min()) < 0 or int(perm.max()) >= N):
+        raise ValueError("perm: entries must lie in [0, N)")
+    loss = torch.empty((L, epochs), dtype=torch.float32, device=theta.device) if want_loss else None
+    cfg = _lib.AdamCfg(lr, beta1, beta2, eps)
+    _lib.check(_lib.lib().bore_lstm_fit(
+        C.byref(desc), L, _lib.ptr(theta), _lib.ptr(m), _lib.ptr(v), _lib.ptr(t), _lib.ptr(X), _lib.ptr(y), N, T,
+        float(mask_value), epochs, int(batch_size), _lib.ptr(perm), C.byref(cfg), _lib.ptr(loss),
+        _lib.stream_ptr()))
+    return loss
+
+
+def lstm_evaluate(desc, theta, X, y, mask_value=1e9):
+    """X [L,N,T,D] f32, y [L,N,T] f32 -> (loss [L] f32, accuracy [L] f32)."""
+    L = theta.shape[0]
+    D = desc.input_dim
+    _chk(theta, torch.float32, (L, lstm_param_count(desc)), "theta")
+    if X.dim() != 4:
+        raise ValueError("X: expected [n_models, N, T, D]")
+    N, T = X.shape[1], X.shape[2]
+    _chk(X, torch.float32, (L, N, T, D), "X")
+    _chk(y, torch.float32, (L, N, T), "y")
+    loss = torch.empty(L, dtype=torch.float32, device=theta.device)
+    acc = torch.empty(L, dtype=torch.float32, device=theta.device)
+    _lib.check(_lib.lib().bore_lstm_evaluate(C.byref(desc), L, _lib.ptr(theta), _lib.ptr(X), _lib.ptr(y), N, T,
+                                             float(mask_value), _lib.ptr(loss), _lib.ptr(acc), _lib.stream_ptr()))
+    return loss, acc

@@ -135,3 +135,172 @@ class BORE(_HyperBand):
             raise ImportError("BORE.run needs the hpbandster package (its Master / nameserver / "
                               "workers); drive `config_generator.get_config(budget)` / "
                               "`.new_result(job)` directly instead")
+
+
+# ------------------------------------------------------------------------------------------------
+# multi-fidelity: bore/plugins/hpbandster/multi_fidelity.py
+# ------------------------------------------------------------------------------------------------
+class SequenceClassifierConfigGenerator(_GeneratorBase):
+    """:95-329.  An LSTM classifier (``StackedRecurrentFactory``) over the rungs of the ladder: the
+    many-to-many network is fitted on the label sequences of every configuration, and a one-to-one
+    network of ``t + 1`` steps, cached per rung, is maximised for the highest rung ``t`` with at least
+    ``num_random_init`` observations.  Same defaults, draw order and logging points as the reference."""
+
+    def __init__(self, config_space, gamma, num_random_init, random_rate, retrain, classifier_kws,
+                 fit_kws, optimizer_kws, seed, **kwargs):
+        super().__init__(**kwargs)
+        from ..data import MultiFidelityRecord
+        from ..layers import l2
+        from ..models import StackedRecurrentFactory
+        from ..transforms import TRANSFORMS
+        assert 0. < gamma < 1., "`gamma` must be in (0, 1)"
+        assert num_random_init > 0, "number of initial random designs must be non-zero!"
+        assert random_rate is None or 0. <= random_rate < 1., "`random_rate` must be in [0, 1)"
+        self.gamma, self.num_random_init, self.random_rate = gamma, num_random_init, random_rate
+        self.config_space = DenseSpace(dense_space_from(config_space).hyperparameters, seed=seed)
+        self.input_dim = self.config_space.get_dimensions(sparse=False)
+        self.bounds = self.config_space.get_bounds()
+        self.optimizer = classifier_kws.get("optimizer", "adam")
+        self.mask_value = classifier_kws.get("mask_value", 1e-9)
+        l2_factor = classifier_kws.get("l2_factor")
+        reg = None if l2_factor is None else l2(l2_factor)
+        # (the reference leaves initialisation and shuffling to TF's global seed; a seeded generator here is
+        # reproducible end to end)
+        self.model_factory = StackedRecurrentFactory(
+            input_dim=self.input_dim, output_dim=1, num_layers=classifier_kws.get("num_layers", 2),
+            num_units=classifier_kws.get("num_units", 32),
+            layer_kws=dict(activation=classifier_kws.get("activation", "elu"), kernel_regularizer=reg,
+                           bias_regularizer=reg), seed=seed)
+        if retrain:
+            raise NotImplementedError
+        self.retrain = retrain
+        self.logit = self._build_compile_network()
+        self.funcs = {}
+        self.batch_size = fit_kws.get("batch_size", 64)
+        self.num_steps_per_iter = fit_kws.get("num_steps_per_iter", 100)
+        self.num_epochs = fit_kws.get("num_epochs")
+        transform_name = optimizer_kws.get("transform", "sigmoid")
+        assert transform_name in TRANSFORMS, f"`transform` must be one of {tuple(TRANSFORMS.keys())}"
+        self.transform = TRANSFORMS.get(transform_name)
+        assert optimizer_kws.get("num_starts") > 0
+        self.num_starts = optimizer_kws.get("num_starts", 5)
+        self.num_samples = optimizer_kws.get("num_samples", 1024)
+        self.method = optimizer_kws.get("method", "L-BFGS-B")
+        self.ftol = optimizer_kws.get("ftol", 1e-9)
+        self.max_iter = optimizer_kws.get("max_iter", 1000)
+        self.distortion = optimizer_kws.get("distortion")
+        self.record = MultiFidelityRecord(gamma=gamma)
+        self.seed = seed
+        self.random_state = np.random.RandomState(seed)
+
+    def _build_compile_network(self):
+        from ..layers import BinaryCrossentropy
+        self.logger.debug("Building and compiling network...")
+        network = self.model_factory.build_many_to_many(mask_value=self.mask_value)
+        network.compile(optimizer=self.optimizer, metrics=["accuracy"], loss=BinaryCrossentropy(from_logits=True))
+        network.summary(print_fn=self.logger.debug)
+        return network
+
+    def _num_epochs(self):
+        """The epochs of one update: ``num_epochs``, or as many whole epochs as ``num_steps_per_iter`` steps
+        over the configurations take."""
+        from ..math import steps_per_epoch
+        if self.num_epochs is not None:
+            return self.num_epochs
+        return self.num_steps_per_iter // steps_per_epoch(self.record.num_features(), self.batch_size)
+
+    def _update_classifier(self):
+        inputs, targets = self.record.sequences(binary=True, pad_value=self.mask_value)
+        self.logger.debug(f"Input sequence shape: {inputs.shape}")
+        self.logger.debug(f"Target sequence shape: {targets.shape}")
+        num_epochs = self._num_epochs()
+        self.logit.fit(inputs, targets, epochs=num_epochs, batch_size=self.batch_size, callbacks=[],
+                       verbose=False)
+        loss, accuracy = self.logit.evaluate(inputs, targets, verbose=False)
+        self.last_fit = (loss, accuracy)
+        self.logger.info(f"[Model fit: loss={loss:.3f}, accuracy={accuracy:.3f}] batch size: {self.batch_size}, "
+                         f"num steps per iter: {self.num_steps_per_iter}, num epochs: {num_epochs}")
+
+    def _is_unique(self, res):
+        is_duplicate = self.record.is_duplicate(res.x)
+        if is_duplicate:
+            self.logger.warning("Duplicate detected! Skipping...")
+        return not is_duplicate
+
+    def get_config(self, budget):
+        """:243-307."""
+        from ..base import maybe_distort
+        config_random_dict = self.config_space.sample_configuration()
+        if self.random_rate is not None and self.random_state.binomial(p=self.random_rate, n=1):
+            self.logger.info(f"[Glob. maximum: skipped (prob={self.random_rate:.2f})] Suggesting random candidate ...")
+            return (config_random_dict, {})
+        t = self.record.highest_rung(min_size=self.num_random_init)
+        if t is None:
+            self.logger.debug(f"There are no rungs with at least {self.num_random_init} observations. "
+                              "Suggesting random candidate...")
+            return (config_random_dict, {})
+        self.logger.debug(f"Rung {t} is the highest with at least {self.num_random_init} observations.")
+        self._update_classifier()
+        if t not in self.funcs:
+            self.funcs[t] = self.model_factory.build_one_to_one(t + 1, transform=self.transform)
+        func = self.funcs[t]
+        opt = func.argmax(self.bounds, num_starts=self.num_starts, num_samples=self.num_samples,
+                          method=self.method, options=dict(maxiter=self.max_iter, ftol=self.ftol),
+                          print_fn=self.logger.debug, filter_fn=self._is_unique, random_state=self.random_state)
+        if opt is None:
+            self.logger.warning("[Glob. maximum: not found!] Either optimization failed in all "
+                                f"{self.num_starts} starts, or all maxima found have been evaluated previously! "
+                                "Suggesting random candidate...")
+            return (config_random_dict, {})
+        loc = opt.x
+        self.logger.info(f"[Glob. maximum: value={-opt.fun:.3f} x={loc}]")
+        config_opt_arr = maybe_distort(loc, self.distortion, self.bounds, self.random_state,
+                                       print_fn=self.logger.info)
+        return (self.config_space.from_array(config_opt_arr), {})
+
+    def new_result(self, job, update_model=True):
+        """:309-329."""
+        super().new_result(job)
+        budget = job.kwargs["budget"]
+        config_arr = self.config_space.to_array(job.kwargs["config"])
+        loss = job.result["loss"]
+        self.record.append(x=config_arr, y=loss, b=budget)
+        self.logger.debug(f"[Data] rungs: {self.record.num_rungs()}, budgets: {self.record.budgets()}, "
+                          f"rung sizes: {self.record.rung_sizes()}")
+        self.logger.debug(f"[Data] thresholds: {self.record.thresholds()}")
+
+
+class BOREHyperband(_HyperBand):
+    """:19-92: HyperBand with ``SequenceClassifierConfigGenerator`` in place of the random generator."""
+
+    def __init__(self, config_space, eta=3, min_budget=0.01, max_budget=1, gamma=None, num_random_init=10,
+                 random_rate=0.1, retrain=False, num_starts=5, num_samples=1024, batch_size=64,
+                 num_steps_per_iter=1000, num_epochs=None, optimizer="adam", mask_value=-1., num_layers=2,
+                 num_units=32, activation="elu", l2_factor=None, transform="sigmoid", method="L-BFGS-B",
+                 max_iter=1000, ftol=1e-9, distortion=None, seed=None, **kwargs):
+        if gamma is None:
+            gamma = 1 / eta
+        cg = SequenceClassifierConfigGenerator(
+            config_space=config_space, gamma=gamma, num_random_init=num_random_init, random_rate=random_rate,
+            retrain=retrain,
+            classifier_kws=dict(num_layers=num_layers, num_units=num_units, l2_factor=l2_factor,
+                                activation=activation, optimizer=optimizer, mask_value=mask_value),
+            fit_kws=dict(batch_size=batch_size, num_steps_per_iter=num_steps_per_iter, num_epochs=num_epochs),
+            optimizer_kws=dict(transform=transform, method=method, max_iter=max_iter, ftol=ftol,
+                               distortion=distortion, num_starts=num_starts, num_samples=num_samples),
+            seed=seed)
+        if HAVE_HPBANDSTER:                             # pragma: no cover
+            super(_HyperBand, self).__init__(config_generator=cg, **kwargs)   # grandparent: Master
+        else:
+            self.config_generator, self.config = cg, {}
+        self.eta, self.min_budget, self.max_budget = eta, min_budget, max_budget
+        self.max_SH_iter = -int(np.log(min_budget / max_budget) / np.log(eta)) + 1
+        self.budgets = max_budget * np.power(eta, -np.linspace(self.max_SH_iter - 1, 0, self.max_SH_iter))
+        self.config.update({'eta': eta, 'min_budget': min_budget, 'max_budget': max_budget,
+                            'budgets': self.budgets, 'max_SH_iter': self.max_SH_iter, 'gamma': gamma,
+                            'num_random_init': num_random_init, 'seed': seed})
+
+    if not HAVE_HPBANDSTER:
+        def run(self, *args, **kwargs):
+            raise ImportError("BOREHyperband.run needs the hpbandster package; drive "
+                              "`config_generator.get_config(budget)` / `.new_result(job)` directly instead")

@@ -483,6 +483,82 @@ int bore_engine_get_stats(bore_engine *engine, bore_engine_stats *out, int reset
  * the outermost run: bore_amd.engine.NativeEngine.close.) */
 void bore_engine_destroy(bore_engine *engine);
 
+/* ---------------------------------------------------------------------------------------------
+ * Multi-fidelity classifier: StackedRecurrentFactory (bore/models.py:48-104) -- n_layers Keras
+ * LSTMCells (gate order i, f, c, o; recurrent activation the logistic sigmoid; `act` on the
+ * candidate and on the cell output) and a linear Dense(1) head, over T steps (the rungs).
+ * Packed parameters in get_weights() order:
+ *   [W_1 (D,4H), U_1 (H,4H), b_1 (4H), ..., W_L, U_L, b_L, W_out (H,1), b_out (1)]
+ * Masking (many-to-many form): step t of a sequence is live iff any feature differs from
+ * mask_value; a masked step keeps h and c and outputs the previous output (Keras RNN over a Masking
+ * layer).  Loss: BCE from logits weighted by the mask and divided by ALL n*T elements (TF 2.5
+ * SUM_OVER_BATCH_SIZE), plus l2 * sum(w^2) for W and b of every cell (never U) and of the head.
+ * Bounds of this build: BORE_LSTM_MAX_* below, and the parameters plus one 64-sequence tile of
+ * state in one CU's LDS (the plugin default D <= 32, 32 units, 2 layers fits); BORE_E_UNSUPPORTED
+ * names the bound otherwise.  Additive to ABI 12.
+ * --------------------------------------------------------------------------------------------- */
+#define BORE_LSTM_MAX_LAYERS 4
+#define BORE_LSTM_MAX_UNITS 64
+#define BORE_LSTM_MAX_STEPS 16
+#define BORE_LSTM_MAX_INPUT 64
+
+typedef struct bore_lstm_desc {
+  int32_t input_dim;                         /* D */
+  int32_t n_layers;                          /* LSTM cells, 1..BORE_LSTM_MAX_LAYERS */
+  int32_t units;                             /* H, the same for every cell */
+  int32_t act;                               /* enum bore_activation of the cells */
+  float l2_kernel[BORE_LSTM_MAX_LAYERS + 1]; /* kernel_regularizer=l2(f) per cell; [n_layers]: the head */
+  float l2_bias[BORE_LSTM_MAX_LAYERS + 1];   /* bias_regularizer=l2(f) per cell; [n_layers]: the head */
+  int32_t output_dim;                        /* must be 1 */
+} bore_lstm_desc;
+
+/* Number of fp32 parameters P; <0 on a bad descriptor.  D=2, H=32, L=2: 12833. */
+int64_t bore_lstm_param_count(const bore_lstm_desc *desc);
+
+/*
+ * predict of both networks.
+ *   many_to_many != 0: X device fp32 [n_models][n_rows][T][D], masked by mask_value
+ *                      -> out device fp32 [n_models][n_rows][T] (logits of every step)
+ *   many_to_many == 0: X device fp32 [n_models][n_rows][D], repeated over T steps, no mask
+ *                      -> out device fp32 [n_models][n_rows] (the last step)
+ * For the same unmasked steps both forms give the same bits.
+ */
+int bore_lstm_forward(const bore_lstm_desc *desc, int n_models, const float *theta, const float *X,
+                      int64_t n_rows, int T, int many_to_many, float mask_value, float *out,
+                      void *stream);
+
+/*
+ * convert(one_to_one, transform): X device fp64 [n_models][n_rows][D], repeated over num_steps
+ * -> val device fp32 [n_models][n_rows] = transform(+-f(x)), grad device fp64 [n_models][n_rows][D]
+ * (the derivative summed over the repeated steps).  transform / negate as bore_mlp_value_and_input_grad.
+ */
+int bore_lstm_value_and_input_grad(const bore_lstm_desc *desc, int n_models, const float *theta,
+                                   const double *X, int64_t n_rows, int num_steps, int transform,
+                                   int negate, float *val, double *grad, void *stream);
+
+/*
+ * fit of the many-to-many network: per epoch the sequences in the order perm[e] gives, in
+ * ceil(N/batch_size) Adam steps (batch_size <= 64); every step of the call in one launch.
+ *   X     device fp32 [n_models][N][T][D];  y device fp32 [n_models][N][T]
+ *   perm  device int32 [n_models][epochs][N], required (bore_shuffle_perm draws them), entries in [0, N)
+ *   theta, adam_m, adam_v, adam_t as bore_mlp_fit (warm start across calls; adam_t advances by
+ *   epochs * ceil(N / batch_size));  epoch_loss device fp32 [n_models][epochs] or NULL: the logged
+ *   loss, batch losses (before each update) averaged with batch-size weights.
+ */
+int bore_lstm_fit(const bore_lstm_desc *desc, int n_models, float *theta, float *adam_m,
+                  float *adam_v, int64_t *adam_t, const float *X, const float *y, int64_t N, int T,
+                  float mask_value, int epochs, int batch_size, const int32_t *perm,
+                  const bore_adam_cfg *adam, float *epoch_loss, void *stream);
+
+/*
+ * evaluate of the many-to-many network: loss (as the fit's, over all N sequences) and
+ * binary accuracy (the logit thresholded at 0.5) averaged over the live elements.
+ *   loss, acc  device fp32 [n_models]
+ */
+int bore_lstm_evaluate(const bore_lstm_desc *desc, int n_models, const float *theta, const float *X,
+                       const float *y, int64_t N, int T, float mask_value, float *loss, float *acc,
+                       void *stream);
+
 #ifdef __cplusplus
 }
 #endif
