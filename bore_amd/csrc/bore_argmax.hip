@@ -85,15 +85,10 @@ extern "C" int bore_labels(int n_models, const double *y, int64_t N, double gamm
   // numpy's virtual index of the default ("linear") method: (n - 1) * q
   const double vi = (double)(N - 1) * gamma;
   const size_t bytes = ((size_t)N + 2) * 8;
-  int rc = allow_lds(labels_kernel, bytes);
-  if (rc) return rc;
   if (g_batch && tau) return fail(BORE_E_INVALID, "labels: no tau output in batch mode");
-  hipLaunchKernelGGL(labels_kernel, dim3(n_models), dim3(BORE_THREADS), bytes, (hipStream_t)stream,
-                     y, (int)N, vi, z, tau, g_batch ? g_batch->ids : nullptr,
-                     g_batch ? g_batch->its : nullptr, g_batch ? g_batch->n_init : 0,
-                     g_batch ? (long long)g_batch->cap : 0LL, gamma);
-  HIP_TRY(hipGetLastError());
-  return 0;
+  return launch_lds(labels_kernel, dim3(n_models), dim3(BORE_THREADS), bytes, stream, y, (int)N, vi, z, tau,
+                    g_batch ? g_batch->ids : nullptr, g_batch ? g_batch->its : nullptr,
+                    g_batch ? g_batch->n_init : 0, g_batch ? (long long)g_batch->cap : 0LL, gamma);
 }
 
 // ---------------------------------------------------------------------------
@@ -430,99 +425,31 @@ static int screen_launch(const bore_mlp_desc *desc, int n_models, const float *t
     if (parts > 64) parts = 64;
     if (forced < 0 ? parts >= 4 : (forced != 0 && parts >= 2)) {
       const bool bf = desc->compute == BORE_COMPUTE_BF16;
-#define BORE_LAUNCH_SPLIT(S, B)                                                                          \
-  {                                                                                                      \
-    if ((rc = allow_lds((screen_topk_kernel<S, B, 1>), off * 4)) ||                                       \
-        (rc = allow_lds((screen_topk_kernel<S, B, 2>), off * 4)))                                         \
-      return rc;                                                                                         \
-    hipLaunchKernelGGL((screen_topk_kernel<S, B, 1>), dim3(n_models, parts), dim3(BORE_THREADS), off * 4, \
-                       (hipStream_t)stream, a);                                                          \
-    hipLaunchKernelGGL((screen_topk_kernel<S, B, 2>), dim3(n_models), dim3(BORE_THREADS), off * 4,        \
-                       (hipStream_t)stream, a);                                                          \
-  }
-      if (!bore_flavour_built(shape)) return fail(BORE_E_UNSUPPORTED, BORE_FLAVOUR_LEFT_OUT);
-#if BORE_ON_3
-      if (shape == 3 && !bf) BORE_LAUNCH_SPLIT(3, false)
-      if (shape == 3 && bf) BORE_LAUNCH_SPLIT(3, true)
-#endif
-#if BORE_ON_4
-      if (shape == 4 && !bf) BORE_LAUNCH_SPLIT(4, false)
-      if (shape == 4 && bf) BORE_LAUNCH_SPLIT(4, true)
-#endif
-#undef BORE_LAUNCH_SPLIT
-      HIP_TRY(hipGetLastError());
-      return 0;
+      return bore_with_flavour(WideFlavours{}, shape, [&](auto S) {
+        auto launch = [&](auto B) {  // (both kernels' LDS limits raised before either is launched)
+          if ((rc = allow_lds(screen_topk_kernel<S(), B(), 1>, off * 4)) ||
+              (rc = allow_lds(screen_topk_kernel<S(), B(), 2>, off * 4)))
+            return rc;
+          hipLaunchKernelGGL((screen_topk_kernel<S(), B(), 1>), dim3(n_models, parts), dim3(BORE_THREADS), off * 4,
+                             (hipStream_t)stream, a);
+          hipLaunchKernelGGL((screen_topk_kernel<S(), B(), 2>), dim3(n_models), dim3(BORE_THREADS), off * 4,
+                             (hipStream_t)stream, a);
+          HIP_TRY(hipGetLastError());
+          return 0;
+        };
+        return !bf ? launch(std::false_type{}) : launch(std::true_type{});
+      });
     }
   }
   if (desc->compute == BORE_COMPUTE_BF16) {
     if (!bore_shape_is_wide(shape)) return fail(BORE_E_UNSUPPORTED, kBf16Shapes);
-    if (!bore_flavour_built(shape)) return fail(BORE_E_UNSUPPORTED, BORE_FLAVOUR_LEFT_OUT);
-#if BORE_ON_3
-    if (shape == 3) {
-      rc = allow_lds((screen_topk_kernel<3, true>), off * 4);
-      if (rc) return rc;
-      hipLaunchKernelGGL((screen_topk_kernel<3, true>), dim3(n_models), dim3(BORE_THREADS), off * 4,
-                         (hipStream_t)stream, a);
-    }
-#endif
-#if BORE_ON_4
-    if (shape == 4) {
-      rc = allow_lds((screen_topk_kernel<4, true>), off * 4);
-      if (rc) return rc;
-      hipLaunchKernelGGL((screen_topk_kernel<4, true>), dim3(n_models), dim3(BORE_THREADS), off * 4,
-                         (hipStream_t)stream, a);
-    }
-#endif
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return bore_with_flavour(WideFlavours{}, shape, [&](auto S) {
+      return launch_lds(screen_topk_kernel<S(), true>, dim3(n_models), dim3(BORE_THREADS), off * 4, stream, a);
+    });
   }
-#define BORE_LAUNCH_SCREEN(S)                                                                 \
-  case S:                                                                                     \
-    rc = allow_lds(screen_topk_kernel<S>, off * 4);                                           \
-    if (rc) return rc;                                                                        \
-    hipLaunchKernelGGL(screen_topk_kernel<S>, dim3(n_models), dim3(BORE_THREADS), off * 4,    \
-                       (hipStream_t)stream, a);                                               \
-    break;
-  if (!bore_flavour_built(shape)) return fail(BORE_E_UNSUPPORTED, BORE_FLAVOUR_LEFT_OUT);
-  switch (shape) {
-#if BORE_ON_1
-    BORE_LAUNCH_SCREEN(1)
-#endif
-#if BORE_ON_2
-    BORE_LAUNCH_SCREEN(2)
-#endif
-#if BORE_ON_3
-    BORE_LAUNCH_SCREEN(3)
-#endif
-#if BORE_ON_4
-    BORE_LAUNCH_SCREEN(4)
-#endif
-#if BORE_ON_5
-    BORE_LAUNCH_SCREEN(5)
-#endif
-#if BORE_ON_N1
-    BORE_LAUNCH_SCREEN(-1)
-#endif
-#if BORE_ON_N2
-    BORE_LAUNCH_SCREEN(-2)
-#endif
-#if BORE_ON_N3
-    BORE_LAUNCH_SCREEN(-3)
-#endif
-#if BORE_ON_N4
-    BORE_LAUNCH_SCREEN(-4)
-#endif
-    default:
-#if !BORE_ON_0
-      return fail(BORE_E_UNSUPPORTED, BORE_FLAVOUR_LEFT_OUT);
-#endif
-#if BORE_ON_0
-    BORE_LAUNCH_SCREEN(0)
-#endif
-  }
-#undef BORE_LAUNCH_SCREEN
-  HIP_TRY(hipGetLastError());
-  return 0;
+  return bore_with_flavour(AcqFlavours{}, shape, [&](auto S) {
+    return launch_lds(screen_topk_kernel<S()>, dim3(n_models), dim3(BORE_THREADS), off * 4, stream, a);
+  });
 }
 
 extern "C" int bore_screen_topk(const bore_mlp_desc *desc, int n_models, const float *theta,
@@ -1404,54 +1331,28 @@ extern "C" int bore_lbfgsb_minimize(const bore_mlp_desc *desc, int n_models, con
   if (rc) return rc;
   if (waves > 4) {  // (wide static shape, more workgroups than CUs: see lbfgsb_build)
     const bool bf = desc->compute == BORE_COMPUTE_BF16;
-#define BORE_LAUNCH_W8(K)                                                                          \
-  {                                                                                                \
-    rc = allow_lds((K), off * 4);                                                                  \
-    if (rc) return rc;                                                                             \
-    hipLaunchKernelGGL((K), dim3(n_models, blocks), dim3(64 * waves), off * 4, (hipStream_t)stream, a); \
-  }
-    if (!bore_flavour_built(flavour)) return fail(BORE_E_UNSUPPORTED, BORE_FLAVOUR_LEFT_OUT);
+    if (!bore_flavour_on(flavour)) return fail(BORE_E_UNSUPPORTED, BORE_FLAVOUR_LEFT_OUT);
     if (!(flavour == 3 || (flavour == 4 && bf) || ((flavour == 2 || flavour == 5) && !bf)))
       return fail(BORE_E_UNSUPPORTED, "lbfgsb_minimize: no many-wave kernel for this flavour");
     // (the kernel whose launch bound covers the waves: a launch of fewer waves than the bound is fine)
-#if BORE_ON_2
-    if (flavour == 2) BORE_LAUNCH_W8((lbfgsb_kernel_w12<2, false>))
-#endif
-#if BORE_ON_5
-    if (flavour == 5) BORE_LAUNCH_W8((lbfgsb_kernel_w12<5, false>))
-#endif
-#if BORE_ON_3
-    if (flavour == 3 && !bf) BORE_LAUNCH_W8((lbfgsb_kernel_w8<3, false>))
-    if (flavour == 3 && bf) BORE_LAUNCH_W8((lbfgsb_kernel_w8<3, true>))
-#endif
-#if BORE_ON_4
-    if (flavour == 4 && bf) BORE_LAUNCH_W8((lbfgsb_kernel_w8<4, true>))
-#endif
-#undef BORE_LAUNCH_W8
-    HIP_TRY(hipGetLastError());
-    return 0;
+    const dim3 grid(n_models, blocks), block(64 * waves);
+    if (!bore_shape_is_wide(flavour))
+      return bore_with_flavour(NarrowWavesFlavours{}, flavour, [&](auto S) {
+        return launch_lds(lbfgsb_kernel_w12<S(), false>, grid, block, off * 4, stream, a);
+      });
+    if (!bf)  // (float32: 16->64-64-64-1 alone has an eight-wave kernel -- 32->128-128-1 was refused above)
+      return bore_with_flavour(FlavourList<3>{}, flavour, [&](auto S) {
+        return launch_lds(lbfgsb_kernel_w8<S(), false>, grid, block, off * 4, stream, a);
+      });
+    return bore_with_flavour(WideFlavours{}, flavour, [&](auto S) {
+      return launch_lds(lbfgsb_kernel_w8<S(), true>, grid, block, off * 4, stream, a);
+    });
   }
   if (desc->compute == BORE_COMPUTE_BF16) {
     if (!bore_shape_is_wide(flavour)) return fail(BORE_E_UNSUPPORTED, kBf16Shapes);
-    if (!bore_flavour_built(flavour)) return fail(BORE_E_UNSUPPORTED, BORE_FLAVOUR_LEFT_OUT);
-#if BORE_ON_3
-    if (flavour == 3) {
-      rc = allow_lds((lbfgsb_kernel<3, true>), off * 4);
-      if (rc) return rc;
-      hipLaunchKernelGGL((lbfgsb_kernel<3, true>), dim3(n_models, blocks), dim3(BORE_THREADS),
-                         off * 4, (hipStream_t)stream, a);
-    }
-#endif
-#if BORE_ON_4
-    if (flavour == 4) {
-      rc = allow_lds((lbfgsb_kernel<4, true>), off * 4);
-      if (rc) return rc;
-      hipLaunchKernelGGL((lbfgsb_kernel<4, true>), dim3(n_models, blocks), dim3(BORE_THREADS),
-                         off * 4, (hipStream_t)stream, a);
-    }
-#endif
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return bore_with_flavour(WideFlavours{}, flavour, [&](auto S) {
+      return launch_lds(lbfgsb_kernel<S(), true>, dim3(n_models, blocks), dim3(BORE_THREADS), off * 4, stream, a);
+    });
   }
   {
     // More workgroups than CUs (many loops x many restarts): the 32-32-1 flavour, whose workgroup
@@ -1461,73 +1362,17 @@ extern "C" int bore_lbfgsb_minimize(const bore_mlp_desc *desc, int n_models, con
     // problem sooner.  BORE_LBFGSB_OCC2 = 0 / 1 forces either (tests, measurements).
     const int forced = getenv("BORE_LBFGSB_OCC2") ? atoi(getenv("BORE_LBFGSB_OCC2")) : -1;
     const bool many = (long long)n_models * blocks > device_cus();
-    (void)forced; (void)many;
     // (one problem per wave only: the kernel does not carry the lane-per-problem loop)
     // (launches with many workgroups of a narrow shape take the twelve-wave kernel above first: lbfgsb_build)
-#define BORE_LAUNCH_OCC2(S)                                                                                                 \
-    if (flavour == (S) && (a.PB <= 4 || a.queue) && off * 4 <= BORE_LDS_BYTES / 2 && (forced < 0 ? many : forced != 0)) { \
-      rc = allow_lds(lbfgsb_kernel_occ2<S>, off * 4);                                                                       \
-      if (rc) return rc;                                                                                                    \
-      hipLaunchKernelGGL(lbfgsb_kernel_occ2<S>, dim3(n_models, blocks), dim3(BORE_THREADS), off * 4,                       \
-                         (hipStream_t)stream, a);                                                                           \
-      HIP_TRY(hipGetLastError());                                                                                           \
-      return 0;                                                                                                             \
-    }
-#if BORE_ON_2
-    BORE_LAUNCH_OCC2(2)
-#endif
-#if BORE_ON_5
-    BORE_LAUNCH_OCC2(5)  // (the plugin's default network: 5 restarts per loop, many loops)
-#endif
-#undef BORE_LAUNCH_OCC2
+    if ((flavour == 2 || flavour == 5) && (a.PB <= 4 || a.queue) && off * 4 <= BORE_LDS_BYTES / 2 &&
+        (forced < 0 ? many : forced != 0))  // (5: the plugin's default network: 5 restarts per loop, many loops)
+      return bore_with_flavour(NarrowWavesFlavours{}, flavour, [&](auto S) {
+        return launch_lds(lbfgsb_kernel_occ2<S()>, dim3(n_models, blocks), dim3(BORE_THREADS), off * 4, stream, a);
+      });
   }
-  if (!bore_flavour_built(flavour)) return fail(BORE_E_UNSUPPORTED, BORE_FLAVOUR_LEFT_OUT);
-#define BORE_LAUNCH_LBFGSB(S)                                                                  \
-  case S:                                                                                      \
-    rc = allow_lds(lbfgsb_kernel<S>, off * 4);                                                 \
-    if (rc) return rc;                                                                         \
-    hipLaunchKernelGGL(lbfgsb_kernel<S>, dim3(n_models, blocks), dim3(BORE_THREADS), off * 4,  \
-                       (hipStream_t)stream, a);                                                \
-    break;
-  switch (flavour) {
-#if BORE_ON_1
-    BORE_LAUNCH_LBFGSB(1)
-#endif
-#if BORE_ON_2
-    BORE_LAUNCH_LBFGSB(2)
-#endif
-#if BORE_ON_3
-    BORE_LAUNCH_LBFGSB(3)
-#endif
-#if BORE_ON_4
-    BORE_LAUNCH_LBFGSB(4)
-#endif
-#if BORE_ON_5
-    BORE_LAUNCH_LBFGSB(5)
-#endif
-#if BORE_ON_N1
-    BORE_LAUNCH_LBFGSB(-1)
-#endif
-#if BORE_ON_N2
-    BORE_LAUNCH_LBFGSB(-2)
-#endif
-#if BORE_ON_N3
-    BORE_LAUNCH_LBFGSB(-3)
-#endif
-#if BORE_ON_N4
-    BORE_LAUNCH_LBFGSB(-4)
-#endif
-    default:
-#if !BORE_ON_0
-      return fail(BORE_E_UNSUPPORTED, BORE_FLAVOUR_LEFT_OUT);
-#endif
-#if BORE_ON_0
-    BORE_LAUNCH_LBFGSB(0)
-#endif
-  }
-#undef BORE_LAUNCH_LBFGSB
-  HIP_TRY(hipGetLastError());
-  return 0;
+  return bore_with_flavour(AcqFlavours{}, flavour, [&](auto S) {
+    return launch_lds(lbfgsb_kernel<S()>, dim3(n_models, blocks), dim3(BORE_THREADS), off * 4, stream, a);
+  });
 }
 
 // ---------------------------------------------------------------------------

@@ -2479,14 +2479,8 @@ static int bore_pads_to_shape(const bore_mlp_desc *d) {
   // (2->16-16-1, 6->32-32-1 and the two fit-only shapes: their static fits give the generic flavour's bits.  The
   // wide 16->64-64-64-1 fit does not -- same tolerance against the oracle, other low bits -- so a net padded onto it would change with the
   // path it takes: left on the generic flavour.)
-  for (int s : {1, 2, 5, BORE_FIT_SHAPE_16_32, BORE_FIT_SHAPE_16_16}) {  // (the fewest zero columns first)
-    if (!bore_flavour_built(s) || d->input_dim >= kShapes[s].D || d->n_layers != kShapes[s].n_layers) continue;
-    bool ok = true;
-    for (int i = 0; i < d->n_layers; ++i)
-      ok = ok && d->units[i] == kShapes[s].units[i] && (kShapes[s].act[0] < 0 || d->act[i] == kShapes[s].act[i]) &&
-           d->l2_kernel[i] == 0.f && d->l2_bias[i] == 0.f;
-    if (ok) return s;
-  }
+  for (int s : {1, 2, 5, BORE_FIT_SHAPE_16_32, BORE_FIT_SHAPE_16_16})  // (the fewest zero columns first)
+    if (bore_flavour_on(s) && d->input_dim < kShapes[s].D && bore_desc_matches(d, s, true, true, true)) return s;
   return 0;
 }
 
@@ -2577,94 +2571,14 @@ extern "C" int bore_mlp_fit(const bore_mlp_desc *desc, int n_models, float *thet
     for (int l = 1; l <= a.L.n_layers; ++l) tiles += (a.L.Np[l - 1] >> 4) * (a.L.Np[l] >> 4);
     const bool can = !g_batch && (shape == 2 || shape == 5 || shape == BORE_FIT_SHAPE_16_32 ||
                                   (shape < 0 && shape >= -4 && a.state_in_lds && tiles > 4));
-    if (can && (forced < 0 ? n_models <= device_cus() : forced != 0)) {
-#define BORE_LAUNCH_FIT_W8(S)                                                                               \
-  case S:                                                                                                   \
-    rc = allow_lds(fit_kernel_w8<S>, off * 4);                                                              \
-    if (rc) return rc;                                                                                      \
-    hipLaunchKernelGGL(fit_kernel_w8<S>, dim3(n_models), dim3(2 * BORE_THREADS), off * 4, (hipStream_t)stream, a); \
-    HIP_TRY(hipGetLastError());                                                                             \
-    return 0;
-      switch (shape) {
-#if BORE_ON_2
-        BORE_LAUNCH_FIT_W8(2)
-#endif
-#if BORE_ON_5
-        BORE_LAUNCH_FIT_W8(5)
-#endif
-#if BORE_ON_6
-        BORE_LAUNCH_FIT_W8(BORE_FIT_SHAPE_16_32)
-#endif
-#if BORE_ON_N1
-        BORE_LAUNCH_FIT_W8(-1)
-#endif
-#if BORE_ON_N2
-        BORE_LAUNCH_FIT_W8(-2)
-#endif
-#if BORE_ON_N3
-        BORE_LAUNCH_FIT_W8(-3)
-#endif
-#if BORE_ON_N4
-        BORE_LAUNCH_FIT_W8(-4)
-#endif
-        default: break;
-      }
-#undef BORE_LAUNCH_FIT_W8
-    }
+    if (can && (forced < 0 ? n_models <= device_cus() : forced != 0))
+      return bore_with_flavour(FitW8Flavours{}, shape, [&](auto S) {
+        return launch_lds(fit_kernel_w8<S()>, dim3(n_models), dim3(2 * BORE_THREADS), off * 4, stream, a);
+      });
   }
-#define BORE_LAUNCH_FIT(S)                                                              \
-  case S:                                                                               \
-    rc = allow_lds(fit_kernel<S>, off * 4);                                             \
-    if (rc) return rc;                                                                  \
-    hipLaunchKernelGGL(fit_kernel<S>, dim3(n_models), dim3(BORE_THREADS), off * 4,      \
-                       (hipStream_t)stream, a);                                         \
-    break;
-  if (!bore_flavour_built(shape)) return fail(BORE_E_UNSUPPORTED, BORE_FLAVOUR_LEFT_OUT);
-  switch (shape) {
-#if BORE_ON_1
-    BORE_LAUNCH_FIT(1)
-#endif
-#if BORE_ON_2
-    BORE_LAUNCH_FIT(2)
-#endif
-#if BORE_ON_3
-    BORE_LAUNCH_FIT(3)
-#endif
-#if BORE_ON_4
-    BORE_LAUNCH_FIT(4)
-#endif
-#if BORE_ON_5
-    BORE_LAUNCH_FIT(5)
-#endif
-#if BORE_ON_6
-    BORE_LAUNCH_FIT(BORE_FIT_SHAPE_16_32)
-#endif
-#if BORE_ON_7
-    BORE_LAUNCH_FIT(BORE_FIT_SHAPE_16_16)
-#endif
-#if BORE_ON_N1
-    BORE_LAUNCH_FIT(-1)
-#endif
-#if BORE_ON_N2
-    BORE_LAUNCH_FIT(-2)
-#endif
-#if BORE_ON_N3
-    BORE_LAUNCH_FIT(-3)
-#endif
-#if BORE_ON_N4
-    BORE_LAUNCH_FIT(-4)
-#endif
-    default:
-#if !BORE_ON_0
-      return fail(BORE_E_UNSUPPORTED, BORE_FLAVOUR_LEFT_OUT);
-#endif
-#if BORE_ON_0
-    BORE_LAUNCH_FIT(0)
-#endif
-  }
-#undef BORE_LAUNCH_FIT
-  HIP_TRY(hipGetLastError());
-  return 0;
+  return bore_with_flavour(FitFlavours{}, shape, [&](auto S) {
+    return launch_lds(fit_kernel<S()>, dim3(n_models), dim3(BORE_THREADS), off * 4, stream, a);
+  });
 }
 
 static int fit_bf16_impl(const bore_mlp_desc *desc, int n_models, float *theta, float *adam_m,
@@ -2722,32 +2636,13 @@ static int fit_bf16_impl(const bore_mlp_desc *desc, int n_models, float *theta, 
   if (off > BORE_LDS_BYTES)
     return fail(BORE_E_UNSUPPORTED, "fit_bf16: weights+images+perm need %zu B of LDS (> %d)", off,
                 BORE_LDS_BYTES);
-  int rc = 0;
-#define BORE_LAUNCH_BF16(KERNEL)                                                             \
-  {                                                                                          \
-    rc = allow_lds(KERNEL, off);                                                             \
-    if (rc) return rc;                                                                       \
-    hipLaunchKernelGGL(KERNEL, dim3(n_models), dim3(BORE_THREADS), off, (hipStream_t)stream, a); \
-  }
-  if (!bore_flavour_built(shape)) return fail(BORE_E_UNSUPPORTED, BORE_FLAVOUR_LEFT_OUT);
-  if (old_form) {
-#if BORE_ON_3
-    if (shape == 3) BORE_LAUNCH_BF16(fit_bf16_kernel<3>)
-#endif
-#if BORE_ON_4
-    if (shape == 4) BORE_LAUNCH_BF16(fit_bf16_kernel<4>)
-#endif
-  } else {
-#if BORE_ON_3
-    if (shape == 3) BORE_LAUNCH_BF16(fit_bf16_mfma_kernel<3>)
-#endif
-#if BORE_ON_4
-    if (shape == 4) BORE_LAUNCH_BF16(fit_bf16_mfma_kernel<4>)
-#endif
-  }
-#undef BORE_LAUNCH_BF16
-  HIP_TRY(hipGetLastError());
-  return 0;
+  if (old_form)
+    return bore_with_flavour(WideFlavours{}, shape, [&](auto S) {
+      return launch_lds(fit_bf16_kernel<S()>, dim3(n_models), dim3(BORE_THREADS), off, stream, a);
+    });
+  return bore_with_flavour(WideFlavours{}, shape, [&](auto S) {
+    return launch_lds(fit_bf16_mfma_kernel<S()>, dim3(n_models), dim3(BORE_THREADS), off, stream, a);
+  });
 }
 
 static int row_launch(bool with_grad, int n_models, RowArgs &a, void *stream) {
@@ -2767,74 +2662,17 @@ static int row_launch(bool with_grad, int n_models, RowArgs &a, void *stream) {
   const long long cap = (2048 + n_models - 1) / n_models;
   if (gy > cap) gy = cap < 1 ? 1 : cap;
   if (gy > 65535) gy = 65535;
-  int rc = 0;
-  const int shape = a.shape;  // (the static flavours keep their row-blocks in registers: no tile)
-#define BORE_LAUNCH_ROWS(G, S)                                                              \
-  {                                                                                         \
-    rc = allow_lds(rows_kernel<G, S>, off * 4);                                             \
-    if (rc) return rc;                                                                      \
-    hipLaunchKernelGGL((rows_kernel<G, S>), dim3(n_models, (unsigned)gy), dim3(BORE_THREADS), \
-                       off * 4, (hipStream_t)stream, a);                                    \
-  }
-#define BORE_LAUNCH_ROWS16(G, S)                                                               \
-  {                                                                                            \
-    rc = allow_lds((rows_kernel<G, S, true>), off * 4);                                        \
-    if (rc) return rc;                                                                         \
-    hipLaunchKernelGGL((rows_kernel<G, S, true>), dim3(n_models, (unsigned)gy),                \
-                       dim3(BORE_THREADS), off * 4, (hipStream_t)stream, a);                   \
-  }
-  if (!bore_flavour_built(shape)) return fail(BORE_E_UNSUPPORTED, BORE_FLAVOUR_LEFT_OUT);
-  if (a.bf16) {  // (the entry points have checked: wide static shape)
-#if BORE_ON_3
-    if (shape == 3 && with_grad) BORE_LAUNCH_ROWS16(true, 3)
-    if (shape == 3 && !with_grad) BORE_LAUNCH_ROWS16(false, 3)
-#endif
-#if BORE_ON_4
-    if (shape == 4 && with_grad) BORE_LAUNCH_ROWS16(true, 4)
-    if (shape == 4 && !with_grad) BORE_LAUNCH_ROWS16(false, 4)
-#endif
-  } else {
-#define BORE_ROWS_BOTH(S)                      \
-  if (shape == (S)) {                          \
-    if (with_grad) BORE_LAUNCH_ROWS(true, S)   \
-    else BORE_LAUNCH_ROWS(false, S)            \
-  }
-#if BORE_ON_1
-    BORE_ROWS_BOTH(1)
-#endif
-#if BORE_ON_2
-    BORE_ROWS_BOTH(2)
-#endif
-#if BORE_ON_3
-    BORE_ROWS_BOTH(3)
-#endif
-#if BORE_ON_4
-    BORE_ROWS_BOTH(4)
-#endif
-#if BORE_ON_5
-    BORE_ROWS_BOTH(5)
-#endif
-#if BORE_ON_N1
-    BORE_ROWS_BOTH(-1)
-#endif
-#if BORE_ON_N2
-    BORE_ROWS_BOTH(-2)
-#endif
-#if BORE_ON_N3
-    BORE_ROWS_BOTH(-3)
-#endif
-#if BORE_ON_N4
-    BORE_ROWS_BOTH(-4)
-#endif
-#if BORE_ON_0
-    BORE_ROWS_BOTH(0)
-#endif
-#undef BORE_ROWS_BOTH
-  }
-#undef BORE_LAUNCH_ROWS
-#undef BORE_LAUNCH_ROWS16
-  HIP_TRY(hipGetLastError());
-  return 0;
+  const dim3 grid(n_models, (unsigned)gy);
+  // (the static flavours keep their row-blocks in registers: no tile)
+  if (a.bf16)  // (the entry points have checked: wide static shape)
+    return bore_with_flavour(WideFlavours{}, a.shape, [&](auto S) {
+      if (with_grad) return launch_lds(rows_kernel<true, S(), true>, grid, dim3(BORE_THREADS), off * 4, stream, a);
+      return launch_lds(rows_kernel<false, S(), true>, grid, dim3(BORE_THREADS), off * 4, stream, a);
+    });
+  return bore_with_flavour(AcqFlavours{}, a.shape, [&](auto S) {
+    if (with_grad) return launch_lds(rows_kernel<true, S()>, grid, dim3(BORE_THREADS), off * 4, stream, a);
+    return launch_lds(rows_kernel<false, S()>, grid, dim3(BORE_THREADS), off * 4, stream, a);
+  });
 }
 
 extern "C" int bore_mlp_forward(const bore_mlp_desc *desc, int n_models, const float *theta,
@@ -2899,12 +2737,7 @@ extern "C" int bore_mlp_evaluate(const bore_mlp_desc *desc, int n_models, const 
   a.total = (int)off;
   off = (off + 3) & ~(size_t)3;
   a.o_layout = (int)off; off += BORE_LAYOUT_FLOATS;
-  rc = allow_lds(evaluate_kernel, off * 4);
-  if (rc) return rc;
-  hipLaunchKernelGGL(evaluate_kernel, dim3(n_models), dim3(BORE_THREADS), off * 4,
-                     (hipStream_t)stream, a);
-  HIP_TRY(hipGetLastError());
-  return 0;
+  return launch_lds(evaluate_kernel, dim3(n_models), dim3(BORE_THREADS), off * 4, stream, a);
 }
 
 extern "C" int bore_shuffle_perm(uint64_t seed, int64_t model_index0, int n_models,
@@ -2918,11 +2751,6 @@ extern "C" int bore_shuffle_perm(uint64_t seed, int64_t model_index0, int n_mode
   // pipelined fit uses inside its steps -- the same permutations
   const int wave_form = N <= 128 && getenv("BORE_SHUFFLE_WAVE") && atoi(getenv("BORE_SHUFFLE_WAVE")) ? 1 : 0;
   const size_t bytes = (wave_form ? (size_t)BORE_PERM_WAVE_FLOATS : (size_t)perm_scratch_floats(N)) * 4;
-  int rc = allow_lds(shuffle_kernel, bytes);
-  if (rc) return rc;
-  hipLaunchKernelGGL(shuffle_kernel, dim3(n_models, epochs), dim3(BORE_THREADS), bytes,
-                     (hipStream_t)stream, seed, (long long)model_index0, (long long)epoch0, epochs,
-                     (int)N, perm, wave_form);
-  HIP_TRY(hipGetLastError());
-  return 0;
+  return launch_lds(shuffle_kernel, dim3(n_models, epochs), dim3(BORE_THREADS), bytes, stream, seed,
+                    (long long)model_index0, (long long)epoch0, epochs, (int)N, perm, wave_form);
 }

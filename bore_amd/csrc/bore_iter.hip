@@ -389,10 +389,17 @@ static int iteration_shape(const bore_mlp_desc *desc) {
   if (desc->compute != BORE_COMPUTE_F32) return 0;
   const int f = bore_kernel_flavour(desc, true);
   if (f == 1) return 1;
-  if (f == 5 && desc->input_dim == 16 && bore_flavour_built(5)) return 5;
+  if (f == 5 && desc->input_dim == 16 && bore_flavour_on(5)) return 5;
   return 0;
 }
 static int iteration_supported(const bore_mlp_desc *desc) { return iteration_shape(desc) != 0; }
+
+// Which of FusedFlavours a build holds: shape 1's fused kernels are in every build (BORE_SHAPE_MASK has never covered
+// them: an experiment build's engine runs 2->16-16-1 whatever else it leaves out), shape 5's follow the mask.
+static constexpr bool fused_flavour_on(int shape) { return shape == 1 || bore_flavour_on(shape); }
+// Loops per CU the fused kernels of a shape are compiled for, at most (template argument OCC; shape 5: one build, two
+// loops per CU with the whole register file of two waves per SIMD)
+static constexpr int fused_most_per_cu(int shape) { return shape == 5 ? 2 : 3; }
 
 // Loops (workgroups) of the fused kernels one CU holds at a time with `lds_bytes` of dynamic LDS each: what the
 // runtime's occupancy query says (registers, waves), and no more than the LDS allows at its allocation granularity
@@ -404,18 +411,17 @@ static int iteration_loops_per_cu(int shape, size_t lds_bytes, int *per_cu_out) 
   int dev = 0;
   HIP_TRY(hipGetDevice(&dev));
   if (seen_bytes != lds_bytes || seen_dev != dev || seen_shape != shape) {  // (per device: a thread may drive several)
-    int per_cu = 0, q_per_cu = 0, most = 3;
-#if BORE_ON_5
-    if (shape == 5) {  // (one build: two loops per CU, the whole register file of two waves per SIMD)
-      HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, iteration_kernel<5, true, 2>, BORE_THREADS, lds_bytes));
-      HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&q_per_cu, queue_kernel<5, 2>, BORE_THREADS, lds_bytes));
-      most = 2;
-    } else
-#endif
-    {
-      HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, iteration_kernel<1, true, 3>, BORE_THREADS, lds_bytes));
-      HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&q_per_cu, queue_kernel<1, 3>, BORE_THREADS, lds_bytes));
-    }
+    int per_cu = 0, q_per_cu = 0;
+    const int most = fused_most_per_cu(shape);
+    // (FusedFlavours with 5 first: this is where the fused kernels are first named, and the order of the names is
+    // the order of the kernels in the code object -- kept as it has been, so that builds can be compared byte for byte)
+    const int rc = bore_with_flavour<fused_flavour_on>(FlavourList<5, 1>{}, shape, [&](auto S) {
+      constexpr int OCC = fused_most_per_cu(S());
+      HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, iteration_kernel<S(), true, OCC>, BORE_THREADS, lds_bytes));
+      HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&q_per_cu, queue_kernel<S(), OCC>, BORE_THREADS, lds_bytes));
+      return 0;
+    });
+    if (rc) return rc;
     if (q_per_cu < per_cu) per_cu = q_per_cu;
     const size_t granule = 1280, static_bytes = 16;  // (s_go4 / s_q4)
     const size_t each = (lds_bytes + static_bytes + granule - 1) / granule * granule;
@@ -476,19 +482,22 @@ static int iteration_launch(const bore_mlp_desc *desc, int n_slots, float *theta
   floats = floats > lb ? floats : lb;
   const size_t labels_floats = 2 * ((size_t)cap + 2);
   floats = floats > labels_floats ? floats : labels_floats;
-  if (shape == 1) {
-    if ((rc = allow_lds(iteration_kernel<1, true, 2>, floats * 4)) || (rc = allow_lds(iteration_kernel<1, true, 3>, floats * 4)) ||
-        (rc = allow_lds(iteration_kernel<1, false, 2>, floats * 4)) || (rc = allow_lds(queue_kernel<1, 2>, floats * 4)) ||
-        (rc = allow_lds(queue_kernel<1, 3>, floats * 4)))
+  // (every kernel the shape may be launched with below, up front)
+  rc = bore_with_flavour<fused_flavour_on>(FusedFlavours{}, shape, [&](auto S) {
+    int rc = 0;
+    if ((rc = allow_lds(iteration_kernel<S(), true, 2>, floats * 4)) || (rc = allow_lds(iteration_kernel<S(), false, 2>, floats * 4)) ||
+        (rc = allow_lds(queue_kernel<S(), 2>, floats * 4)))
       return rc;
-  }
-#if BORE_ON_5
-  if (shape == 5) {
-    if ((rc = allow_lds(iteration_kernel<5, true, 2>, floats * 4)) || (rc = allow_lds(iteration_kernel<5, false, 2>, floats * 4)) ||
-        (rc = allow_lds(queue_kernel<5, 2>, floats * 4)))
-      return rc;
-  }
-#endif
+    if constexpr (fused_most_per_cu(S()) == 3)
+      if ((rc = allow_lds(iteration_kernel<S(), true, 3>, floats * 4)) || (rc = allow_lds(queue_kernel<S(), 3>, floats * 4))) return rc;
+    return 0;
+  });
+  if (rc) return rc;
+  auto launch = [&](auto kernel, int workgroups) {
+    hipLaunchKernelGGL(kernel, dim3(workgroups), dim3(BORE_THREADS), floats * 4, (hipStream_t)stream, d_args);
+    HIP_TRY(hipGetLastError());
+    return 0;
+  };
   if (per_cu_out) {  // (a question, not a launch: how many loops of this model one CU holds)
     *per_cu_out = 0;
     return iteration_loops_per_cu(shape, floats * 4, per_cu_out);
@@ -500,18 +509,12 @@ static int iteration_launch(const bore_mlp_desc *desc, int n_slots, float *theta
     h->wait_ticks = 0;
     HIP_TRY(hipMemcpyAsync(const_cast<IterArgs *>(d_args), h, sizeof(IterArgs), hipMemcpyHostToDevice,
                            (hipStream_t)stream));
-    // (no more workgroups than two per CU: the kernel with the whole register file)
-#if BORE_ON_5
-    if (shape == 5)
-      hipLaunchKernelGGL((queue_kernel<5, 2>), dim3(queue_wgs), dim3(BORE_THREADS), floats * 4, (hipStream_t)stream, d_args);
-    else
-#endif
-    if (queue_wgs <= 2 * device_cus())
-      hipLaunchKernelGGL((queue_kernel<1, 2>), dim3(queue_wgs), dim3(BORE_THREADS), floats * 4, (hipStream_t)stream, d_args);
-    else
-      hipLaunchKernelGGL((queue_kernel<1, 3>), dim3(queue_wgs), dim3(BORE_THREADS), floats * 4, (hipStream_t)stream, d_args);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return bore_with_flavour<fused_flavour_on>(FusedFlavours{}, shape, [&](auto S) {
+      // (no more workgroups than two per CU: the kernel with the whole register file)
+      if constexpr (fused_most_per_cu(S()) == 3)
+        if (queue_wgs > 2 * device_cus()) return launch(queue_kernel<S(), 3>, queue_wgs);
+      return launch(queue_kernel<S(), 2>, queue_wgs);
+    });
   }
   if (h->wait_ticks > 0) {  // waiting workgroups hold their slots: only when all of them fit at once
     int per_cu = 0;
@@ -523,27 +526,10 @@ static int iteration_launch(const bore_mlp_desc *desc, int n_slots, float *theta
   // h heads the caller's staging block (arguments | per-slot inputs | index lists): one upload
   HIP_TRY(hipMemcpyAsync(const_cast<IterArgs *>(d_args), h, upload_bytes, hipMemcpyHostToDevice,
                          (hipStream_t)stream));
-#if BORE_ON_5
-  if (shape == 5) {
-    if (h->wait_ticks > 0)
-      hipLaunchKernelGGL((iteration_kernel<5, true, 2>), dim3(n_slots), dim3(BORE_THREADS), floats * 4,
-                         (hipStream_t)stream, d_args);
-    else
-      hipLaunchKernelGGL((iteration_kernel<5, false, 2>), dim3(n_slots), dim3(BORE_THREADS), floats * 4,
-                         (hipStream_t)stream, d_args);
-    HIP_TRY(hipGetLastError());
-    return 0;
-  }
-#endif
-  if (h->wait_ticks > 0 && g_batch->resident_loops > 2 * device_cus())  // (three loops per CU: see iteration_kernel)
-    hipLaunchKernelGGL((iteration_kernel<1, true, 3>), dim3(n_slots), dim3(BORE_THREADS), floats * 4,
-                       (hipStream_t)stream, d_args);
-  else if (h->wait_ticks > 0)
-    hipLaunchKernelGGL((iteration_kernel<1, true, 2>), dim3(n_slots), dim3(BORE_THREADS), floats * 4,
-                       (hipStream_t)stream, d_args);
-  else
-    hipLaunchKernelGGL((iteration_kernel<1, false, 2>), dim3(n_slots), dim3(BORE_THREADS), floats * 4,
-                       (hipStream_t)stream, d_args);
-  HIP_TRY(hipGetLastError());
-  return 0;
+  return bore_with_flavour<fused_flavour_on>(FusedFlavours{}, shape, [&](auto S) {
+    if constexpr (fused_most_per_cu(S()) == 3)  // (three loops per CU: see iteration_kernel)
+      if (h->wait_ticks > 0 && g_batch->resident_loops > 2 * device_cus()) return launch(iteration_kernel<S(), true, 3>, n_slots);
+    if (h->wait_ticks > 0) return launch(iteration_kernel<S(), true, 2>, n_slots);
+    return launch(iteration_kernel<S(), false, 2>, n_slots);
+  });
 }

@@ -437,7 +437,7 @@ extern "C" int bore_svgd_optimize(const bore_mlp_desc *desc, int n_models, const
   const int flav = bore_kernel_flavour(desc, true);
   const bool bf = desc->compute == BORE_COMPUTE_BF16;
   if (bf && !bore_shape_is_wide(flav)) return fail(BORE_E_UNSUPPORTED, kBf16Shapes);
-  if (bf && !bore_flavour_built(flav)) return fail(BORE_E_UNSUPPORTED, BORE_FLAVOUR_LEFT_OUT);
+  if (bf && !bore_flavour_on(flav)) return fail(BORE_E_UNSUPPORTED, BORE_FLAVOUR_LEFT_OUT);
   const int D = desc->input_dim, n = n_particles;
   if (D < 1 || D > BORE_DIM_MAX) return fail(BORE_E_UNSUPPORTED, "svgd_optimize: input_dim must be 1..%d", BORE_DIM_MAX);
   if (n < 1 || n > BORE_SVGD_MAX_PARTICLES)  // (what fits is decided by the LDS check below: 32 n D bytes of state)
@@ -483,24 +483,10 @@ extern "C" int bore_svgd_optimize(const bore_mlp_desc *desc, int n_models, const
   if (off * 4 > BORE_LDS_BYTES)
     return fail(BORE_E_UNSUPPORTED, "svgd_optimize: %d particles in %d dimensions need %zu B of LDS (> %d)",
                 n, D, off * 4, BORE_LDS_BYTES);
-  int rc = 0;
-#define BORE_SVGD_LAUNCH(BF)                                                                                   \
-  do {                                                                                                         \
-    rc = big ? allow_lds(svgd_big_kernel<BF>, off * 4) : allow_lds(svgd_kernel<BF>, off * 4);                  \
-    if (rc) return rc;                                                                                         \
-    if (big)                                                                                                   \
-      hipLaunchKernelGGL(svgd_big_kernel<BF>, dim3(n_models), dim3(BORE_THREADS), off * 4, (hipStream_t)stream, a); \
-    else                                                                                                       \
-      hipLaunchKernelGGL(svgd_kernel<BF>, dim3(n_models), dim3(BORE_THREADS), off * 4, (hipStream_t)stream, a); \
-  } while (0)
-  if (!bf) BORE_SVGD_LAUNCH(0);
-#if BORE_ON_3
-  else if (flav == 3) BORE_SVGD_LAUNCH(3);
-#endif
-#if BORE_ON_4
-  else if (flav == 4) BORE_SVGD_LAUNCH(4);
-#endif
-#undef BORE_SVGD_LAUNCH
-  HIP_TRY(hipGetLastError());
-  return 0;
+  auto launch = [&](auto BF) {  // (BF: 0 = a float32 network, 3 / 4 = the bfloat16 image of that wide shape)
+    if (big) return launch_lds(svgd_big_kernel<BF()>, dim3(n_models), dim3(BORE_THREADS), off * 4, stream, a);
+    return launch_lds(svgd_kernel<BF()>, dim3(n_models), dim3(BORE_THREADS), off * 4, stream, a);
+  };
+  if (!bf) return launch(std::integral_constant<int, 0>{});
+  return bore_with_flavour(WideFlavours{}, flav, launch);
 }

@@ -58,6 +58,15 @@ inline int allow_lds(K kernel, size_t bytes) {
   return 0;
 }
 
+// One launch: the kernel's LDS limit raised to what it asks for, the launch, the launch's error.
+template <typename K, typename... Args>
+inline int launch_lds(K kernel, dim3 grid, dim3 block, size_t lds_bytes, void *stream, const Args &...args) {
+  if (const int rc = allow_lds(kernel, lds_bytes)) return rc;
+  hipLaunchKernelGGL(kernel, grid, block, lds_bytes, (hipStream_t)stream, args...);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 // Compute units of the current device (per device, cached).
 inline int device_cus() {
   static int cus[64];

@@ -7,6 +7,9 @@
 // expression: layer loops unroll, offsets fold into ds_read immediates, the k-loops of
 // the MFMA tiles have constant trip counts.  SHAPE 0 is the generic path.
 #pragma once
+#include <type_traits>
+
+#include "host_common.h"
 #include "mlp_layout.h"
 
 #define BORE_N_SHAPES 5  // ids 1..BORE_N_SHAPES: every kernel family (fit, rows, screen, restarts, ...)
@@ -23,22 +26,11 @@
 // -DBORE_SHAPE_MASK=0x2 compiles the 2->16-16-1 kernels alone in a fifth of the time; a request for
 // a flavour that was left out is refused with BORE_E_UNSUPPORTED).  Bit 0: the generic flavour 0,
 // bits 1..5: static shapes 1..5, bits 6..9: flavours -1..-4, bits 10, 11: the fit-only shapes 6, 7.  The shipped
-// library has them all.
+// library has them all.  bore_flavour_on() is the one place that reads the mask; which flavours a kernel FAMILY has
+// is a FlavourList below, and bore_with_flavour() instantiates a family's kernel for the listed flavours that are on.
 #ifndef BORE_SHAPE_MASK
 #define BORE_SHAPE_MASK 0xfff
 #endif
-#define BORE_ON_0 ((BORE_SHAPE_MASK) & 0x001)
-#define BORE_ON_1 ((BORE_SHAPE_MASK) & 0x002)
-#define BORE_ON_2 ((BORE_SHAPE_MASK) & 0x004)
-#define BORE_ON_3 ((BORE_SHAPE_MASK) & 0x008)
-#define BORE_ON_4 ((BORE_SHAPE_MASK) & 0x010)
-#define BORE_ON_5 ((BORE_SHAPE_MASK) & 0x020)
-#define BORE_ON_N1 ((BORE_SHAPE_MASK) & 0x040)
-#define BORE_ON_N2 ((BORE_SHAPE_MASK) & 0x080)
-#define BORE_ON_N3 ((BORE_SHAPE_MASK) & 0x100)
-#define BORE_ON_N4 ((BORE_SHAPE_MASK) & 0x200)
-#define BORE_ON_6 ((BORE_SHAPE_MASK) & 0x400)
-#define BORE_ON_7 ((BORE_SHAPE_MASK) & 0x800)
 #define BORE_FLAVOUR_LEFT_OUT "this build of the library leaves the kernel flavour out (BORE_SHAPE_MASK)"
 
 struct ShapeSpec {
@@ -98,17 +90,24 @@ struct StaticLayout {
   static constexpr MlpLayout value = bore_static_layout(SHAPE, DELTAS, ROWS);
 };
 
+// Does the descriptor have the widths of static shape s?  The input dimension equal to the shape's, or at most it
+// (`fewer_inputs`: the kernels run such a net zero-padded); `acts`: the shape's activations too, where it fixes them;
+// `no_l2`: and no regulariser.
+static inline bool bore_desc_matches(const bore_mlp_desc *d, int s, bool fewer_inputs, bool acts, bool no_l2) {
+  if ((fewer_inputs ? d->input_dim > kShapes[s].D : d->input_dim != kShapes[s].D) || d->n_layers != kShapes[s].n_layers)
+    return false;
+  bool ok = true;
+  for (int i = 0; i < d->n_layers; ++i)
+    ok = ok && d->units[i] == kShapes[s].units[i] &&
+         (!acts || kShapes[s].act[0] < 0 || d->act[i] == kShapes[s].act[i]) &&
+         (!no_l2 || (d->l2_kernel[i] == 0.f && d->l2_bias[i] == 0.f));
+  return ok;
+}
+
 // Which static shape (if any) a descriptor matches: same widths and activations, no l2.
 static inline int bore_match_shape(const bore_mlp_desc *d) {
-  for (int s = 1; s <= BORE_N_SHAPES; ++s) {
-    if (d->input_dim != kShapes[s].D || d->n_layers != kShapes[s].n_layers) continue;
-    bool ok = true;
-    for (int i = 0; i < d->n_layers; ++i)
-      ok = ok && d->units[i] == kShapes[s].units[i] &&
-           (kShapes[s].act[0] < 0 || d->act[i] == kShapes[s].act[i]) &&
-           d->l2_kernel[i] == 0.f && d->l2_bias[i] == 0.f;
-    if (ok) return s;
-  }
+  for (int s = 1; s <= BORE_N_SHAPES; ++s)
+    if (bore_desc_matches(d, s, false, true, true)) return s;
   return 0;
 }
 
@@ -133,13 +132,8 @@ static constexpr bool bore_shape_takes_fewer_inputs(int shape) { return shape ==
 static inline int bore_acq_flavour(const bore_mlp_desc *d, bool full_tile) {
   const int f = bore_kernel_flavour(d, full_tile);
   if (f > 0 || !full_tile || d->compute != BORE_COMPUTE_F32) return f;
-  for (int s : {5}) {
-    if (d->input_dim > kShapes[s].D || d->n_layers != kShapes[s].n_layers) continue;
-    bool ok = true;
-    for (int i = 0; i < d->n_layers; ++i)
-      ok = ok && d->units[i] == kShapes[s].units[i] && (kShapes[s].act[0] < 0 || d->act[i] == kShapes[s].act[i]);
-    if (ok) return s;
-  }
+  for (int s : {5})
+    if (bore_desc_matches(d, s, true, true, false)) return s;
   return f;
 }
 
@@ -147,18 +141,37 @@ static inline int bore_acq_flavour(const bore_mlp_desc *d, bool full_tile) {
 static inline int bore_fit_flavour(const bore_mlp_desc *d, bool full_tile) {
   const int f = bore_kernel_flavour(d, full_tile);
   if (f > 0 || !full_tile) return f;
-  for (int s = BORE_N_SHAPES + 1; s <= BORE_N_SHAPES + BORE_N_FIT_SHAPES; ++s) {
-    if (d->input_dim != kShapes[s].D || d->n_layers != kShapes[s].n_layers) continue;
-    bool ok = true;
-    for (int i = 0; i < d->n_layers; ++i)
-      ok = ok && d->units[i] == kShapes[s].units[i] && d->l2_kernel[i] == 0.f && d->l2_bias[i] == 0.f;
-    if (ok) return s;
-  }
+  for (int s = BORE_N_SHAPES + 1; s <= BORE_N_SHAPES + BORE_N_FIT_SHAPES; ++s)
+    if (bore_desc_matches(d, s, false, false, true)) return s;
   return f;
 }
 
-// (experiment builds: was this flavour compiled in?)
-static inline bool bore_flavour_built(int flavour) {
-  const int bit = flavour > BORE_N_SHAPES ? 4 + flavour : (flavour >= 0 ? flavour : 5 - flavour);  // (6, 7 -> 10, 11)
+// Was this flavour compiled in?  (BORE_SHAPE_MASK's bit of a flavour: 0..5 -> 0..5, -1..-4 -> 6..9, 6, 7 -> 10, 11)
+static constexpr bool bore_flavour_on(int flavour) {
+  const int bit = flavour > BORE_N_SHAPES ? 4 + flavour : (flavour >= 0 ? flavour : 5 - flavour);
   return ((BORE_SHAPE_MASK) >> bit) & 1;
+}
+
+// The flavours each kernel family is instantiated for.
+template <int... S>
+struct FlavourList {};
+using AcqFlavours = FlavourList<1, 2, 3, 4, 5, -1, -2, -3, -4, 0>;  // rows, screening, restarts
+using FitFlavours = FlavourList<1, 2, 3, 4, 5, BORE_FIT_SHAPE_16_32, BORE_FIT_SHAPE_16_16, -1, -2, -3, -4, 0>;
+using FitW8Flavours = FlavourList<2, 5, BORE_FIT_SHAPE_16_32, -1, -2, -3, -4>;  // the eight-wave fit
+using WideFlavours = FlavourList<3, 4>;        // bfloat16 kernels, the split screen, the eight-wave restarts
+using NarrowWavesFlavours = FlavourList<2, 5>; // the twelve-wave and the two-per-CU restarts
+using FusedFlavours = FlavourList<1, 5>;       // the fused iteration and work-queue kernels (bore_iter.hip)
+
+// Calls f(std::integral_constant<int, S>{}) for the listed flavour S equal to `flavour` and returns its result; a
+// flavour that is not listed, or that this build leaves out, is refused.  f is instantiated for the flavours that are
+// on and no others, so a masked build holds no kernel of the others.  (ON: the fused kernels' own rule, bore_iter.hip)
+template <bool (*ON)(int) = bore_flavour_on, class F>
+inline int bore_with_flavour(FlavourList<>, int, F &&) {
+  return fail(BORE_E_UNSUPPORTED, BORE_FLAVOUR_LEFT_OUT);
+}
+template <bool (*ON)(int) = bore_flavour_on, int S0, int... S, class F>
+inline int bore_with_flavour(FlavourList<S0, S...>, int flavour, F &&f) {
+  if constexpr (ON(S0))
+    if (flavour == S0) return f(std::integral_constant<int, S0>{});
+  return bore_with_flavour<ON>(FlavourList<S...>{}, flavour, f);
 }
