@@ -18,7 +18,7 @@ CSRC = os.path.join(_HERE, "csrc")
 # only ever LOADED: build_native() writes the default path and nothing else.)
 DEFAULT_LIB_PATH = os.path.join(CSRC, "libbore_hip.so")
 LIB_PATH = os.environ.get("BORE_LIB_PATH") or DEFAULT_LIB_PATH
-SOURCES = ["bore_all.hip"]   # a unity build of bore_{hip,argmax,svgd,iter,engine}.hip
+SOURCES = ["bore_all.hip"]   # a unity build of bore_{hip,argmax,svgd,iter,engine,lstm,stream}.hip
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "bore_hip.h")
 
 # The replica engine runs up to a dozen independent launches on as many HIP streams; ROCm gives a
@@ -28,6 +28,7 @@ os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 
 MAX_LAYERS = 8
 BATCH_MAX = 64
+STREAM_MAX_UNITS = 512   # include/bore_hip.h BORE_STREAM_MAX_UNITS
 
 ACT = dict(linear=0, relu=1, elu=2, sigmoid=3, tanh=4)
 TRANSFORM = dict(identity=0, sigmoid=1, exp=2)
@@ -41,7 +42,7 @@ EXPORTS = [
     "bore_svgd_optimize", "bore_set_batch", "bore_engine_create", "bore_engine_run", "bore_engine_size", "bore_engine_observations",
     "bore_engine_state", "bore_engine_get_stats", "bore_engine_destroy", "bore_objective_branin01",
     "bore_lstm_param_count", "bore_lstm_forward", "bore_lstm_value_and_input_grad", "bore_lstm_fit",
-    "bore_lstm_evaluate",
+    "bore_lstm_evaluate", "bore_mlp_streamed",
 ]
 
 
@@ -242,6 +243,7 @@ def lib():
     L.bore_lstm_fit.argtypes = [lp, i32, vp, vp, vp, vp, vp, vp, i64, i32, f32, i32, i32, vp,
                                 C.POINTER(AdamCfg), vp, vp]
     L.bore_lstm_evaluate.argtypes = [lp, i32, vp, vp, vp, i64, i32, f32, vp, vp, vp]
+    L.bore_mlp_streamed.argtypes = [dp]
     for name in EXPORTS:
         if name not in ("bore_last_error", "bore_param_count", "bore_lstm_param_count", "bore_engine_size",
                         "bore_engine_destroy", "bore_set_batch"):

@@ -7,3 +7,4 @@
 #include "bore_iter.hip"
 #include "bore_engine.hip"
 #include "bore_lstm.hip"
+#include "bore_stream.hip"

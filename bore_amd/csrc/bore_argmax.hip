@@ -1204,7 +1204,9 @@ static int lbfgsb_build(const bore_mlp_desc *desc, int n_models, const float *th
   const int shape = flavour > 0 ? flavour : 0;  // constexpr-layout kernels assume a 64-row tile
   size_t off = 0;
   for (;; --PB) {
-    if (PB < 1) return fail(BORE_E_UNSUPPORTED, "lbfgsb_minimize: one problem's state does not fit in LDS");
+    if (PB < 1)
+      return fail(BORE_E_UNSUPPORTED, "lbfgsb_minimize: one problem's state does not fit in LDS beside the network; %s",
+                  kStreamedElsewhere);
     // static flavours keep the row-blocks in registers; their tile region only stages the
     // points (A_0) and gradients (D_0) of waves that run several problems: 2 x 64 rows
     const int rows = shape ? 16 : 16 * (PB < 4 ? PB : 4);

@@ -2302,6 +2302,21 @@ static int fit_bf16_impl(const bore_mlp_desc *, int, float *, float *, float *, 
                          const float *, const float *, int64_t, int, int, const int32_t *, uint64_t,
                          int64_t, int64_t, const bore_adam_cfg *, float *, void *);
 
+// The streamed flavour (bore_stream.hip): float32 networks whose parameters stay in global memory.  An entry point
+// below goes there exactly when its own LDS check refuses the network for capacity, or when BORE_STREAM=1 asks.
+static bool stream_forced(const bore_mlp_desc *);
+static int stream_forward_entry(const bore_mlp_desc *, int, const float *, const float *, int64_t, int, float *, void *);
+static int stream_value_and_input_grad(const bore_mlp_desc *, int, const float *, const double *, int64_t, int, int,
+                                       float *, double *, void *);
+static int stream_evaluate(const bore_mlp_desc *, int, const float *, const float *, const float *, int64_t, float *,
+                           float *, void *);
+static int stream_fit(const bore_mlp_desc *, int, float *, float *, float *, int64_t *, const float *, const float *,
+                      int64_t, int, int, const int32_t *, uint64_t, int64_t, int64_t, const bore_adam_cfg *, float *,
+                      void *);
+static bool stream_takes(const bore_mlp_desc *desc, int rc) {
+  return rc == BORE_E_UNSUPPORTED && desc && desc->compute == BORE_COMPUTE_F32 && !g_batch;
+}
+
 // Arguments, LDS bytes and kernel flavour of a float32 fit launch (what bore_mlp_fit launches;
 // the fused iteration kernel of bore_iter.hip builds its fit phase with it).  Returns 1 when
 // there is nothing to do (epochs == 0).
@@ -2542,6 +2557,10 @@ extern "C" int bore_mlp_fit(const bore_mlp_desc *desc, int n_models, float *thet
                             int64_t N, int epochs, int batch_size, const int32_t *perm,
                             uint64_t seed, int64_t model_index0, int64_t epoch0,
                             const bore_adam_cfg *adam, float *epoch_loss, void *stream) {
+  // (BORE_STREAM = 1: in front of everything, the zero-padded detour included)
+  if (stream_forced(desc))
+    return stream_fit(desc, n_models, theta, adam_m, adam_v, adam_t, X, z, N, epochs, batch_size, perm, seed,
+                      model_index0, epoch0, adam, epoch_loss, stream);
   // (BORE_FIT_PAD = 0: such nets on the generic flavour, as before round 4 -- A/B, tests)
   if (desc && !g_batch && theta && adam_m && adam_v && adam_t && X && z && adam && epochs > 0 && n_models >= 1 &&
       N >= 1 && batch_size == BORE_BATCH_MAX && !(getenv("BORE_FIT_PAD") && !atoi(getenv("BORE_FIT_PAD")))) {
@@ -2562,6 +2581,9 @@ extern "C" int bore_mlp_fit(const bore_mlp_desc *desc, int n_models, float *thet
   int shape = 0;
   int rc = fit_build(desc, n_models, theta, adam_m, adam_v, adam_t, X, z, N, epochs, batch_size, perm,
                      seed, model_index0, epoch0, adam, epoch_loss, a, off, shape);
+  if (stream_takes(desc, rc))  // (refused for capacity: the streamed flavour, or its own bound by name)
+    return stream_fit(desc, n_models, theta, adam_m, adam_v, adam_t, X, z, N, epochs, batch_size, perm, seed,
+                      model_index0, epoch0, adam, epoch_loss, stream);
   if (rc) return rc < 0 ? rc : 0;
   {  // Eight waves (fit_kernel_w8): 6->32-32-1, and any net of up to four layers with more than four weight-gradient
      // tiles whose Adam slots are in LDS -- launches with no more models than CUs.  BORE_FIT_W8 = 0 / 1 forces the
@@ -2679,8 +2701,10 @@ extern "C" int bore_mlp_forward(const bore_mlp_desc *desc, int n_models, const f
                                 const float *X, int64_t n_rows, int x_shared, float *out,
                                 void *stream) {
   RowArgs a;
+  if (stream_forced(desc)) return stream_forward_entry(desc, n_models, theta, X, n_rows, x_shared, out, stream);
   int rc = check_common(desc, n_models, 0, BORE_BATCH_MAX, true,
                         BORE_BATCH_MAX + BORE_LAYOUT_FLOATS + 4, &a.L);
+  if (stream_takes(desc, rc)) return stream_forward_entry(desc, n_models, theta, X, n_rows, x_shared, out, stream);
   if (rc) return rc;
   if (a.L.w[a.L.n_layers] != 1)
     return fail(BORE_E_INVALID, "forward: the last Dense layer must have 1 unit");
@@ -2701,8 +2725,12 @@ extern "C" int bore_mlp_value_and_input_grad(const bore_mlp_desc *desc, int n_mo
                                              int transform, int negate, float *val,
                                              double *grad, void *stream) {
   RowArgs a;
+  if (stream_forced(desc))
+    return stream_value_and_input_grad(desc, n_models, theta, X, n_rows, transform, negate, val, grad, stream);
   int rc = check_common(desc, n_models, 2, BORE_BATCH_MAX, true,
                         BORE_BATCH_MAX + BORE_LAYOUT_FLOATS + 4, &a.L);
+  if (stream_takes(desc, rc))
+    return stream_value_and_input_grad(desc, n_models, theta, X, n_rows, transform, negate, val, grad, stream);
   if (rc) return rc;
   if (a.L.w[a.L.n_layers] != 1)
     return fail(BORE_E_INVALID, "value_and_input_grad: the last Dense layer must have 1 unit");
@@ -2724,7 +2752,9 @@ extern "C" int bore_mlp_evaluate(const bore_mlp_desc *desc, int n_models, const 
                                  const float *X, const float *z, int64_t N, float *loss,
                                  float *acc, void *stream) {
   EvalArgs a;
+  if (stream_forced(desc)) return stream_evaluate(desc, n_models, theta, X, z, N, loss, acc, stream);
   int rc = check_common(desc, n_models, 0, BORE_BATCH_MAX, true, 8 + BORE_LAYOUT_FLOATS + 4, &a.L);
+  if (stream_takes(desc, rc)) return stream_evaluate(desc, n_models, theta, X, z, N, loss, acc, stream);
   if (rc) return rc;
   if (a.L.w[a.L.n_layers] != 1)
     return fail(BORE_E_INVALID, "evaluate: the last Dense layer must have 1 unit");

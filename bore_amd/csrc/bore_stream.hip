@@ -1,0 +1,636 @@
+// bore_stream.hip -- the STREAMED flavour: float32 Dense stacks whose parameters do not fit one
+// workgroup's LDS (mlp_layout.h) stay in global memory -- L2-resident in practice, 3.2 MB at
+// 512-512-512 -- and pass through LDS in panels.  Serves bore_mlp_forward, bore_mlp_evaluate,
+// bore_mlp_value_and_input_grad and bore_mlp_fit; an entry point comes here exactly when its own LDS
+// check refuses the network for capacity (or BORE_STREAM=1 asks for it: tests run both flavours on
+// the same inputs).
+//
+// Every matrix product of the path is one routine, stream_gemm: C[M x N] = sum_r A(i, r) B(r, j) with
+// both operands in global memory, either of them read transposed.  A 64 x 128 output tile at a time:
+// the workgroup stages a 64 x 32 panel of A and a 32 x 128 panel of B into LDS (double-buffered: the
+// next panel's loads are in flight under the current panel's MFMAs, one barrier per panel), wave w owns
+// rows [16 w, 16 w + 16) of the tile and keeps eight 16 x 16 accumulators (eight independent
+// v_mfma_f32_16x16x4_f32 chains).  An output element is ONE fmaf chain over r in ascending order,
+// whatever the tiling and whichever rows share the tile: a row alone gives the bits it gives in a batch,
+// a model alone the bits it gives in a multi-model launch.  No float atomics anywhere.
+//
+// Activations and deltas of the current 64-row tile live in a stream-ordered device workspace
+// (hipMallocAsync; at 8 x 512 x 64 rows they do not fit LDS), written once and read once per product.
+// Data that one wave writes and another wave of the SAME workgroup reads (activations, deltas, theta
+// after an Adam update) is handed over by __syncthreads(): a workgroup-scope release / acquire around
+// the barrier.  No workgroup ever waits for another one.
+#include <hip/hip_runtime.h>
+
+#include <cstdlib>
+
+#include "host_common.h"
+#include "mlp_device.h"
+
+namespace bore {
+
+constexpr int SKP = 32;          // reduction depth of a panel
+constexpr int SNC = 128;         // output columns per pass: 8 accumulators per wave
+constexpr int SROWS = BORE_BATCH_MAX;
+constexpr int SLDA = SKP + 2;    // 2 * odd: the 16-row x 4-k operand fetch hits distinct banks
+constexpr int SLDB = SNC + 16;   // the four k-rows of an operand fetch land 16 banks apart
+constexpr long long STREAM_WS_BYTES = 64ll << 20;  // the rows kernels' workspace per call (one tile per model at least)
+
+struct StreamLds {
+  float a[2][SROWS * SLDA];
+  float b[2][SKP * SLDB];
+  int layout[(sizeof(MlpLayout) + 3) / 4];
+  int pre[BORE_MAX_LAYERS + 2];  // pre[l] = w[0] + .. + w[l-1]: where A_l / D_l start in the workspace
+  float zt[SROWS];               // labels of the tile rows (fit, evaluate)
+  float red[BORE_THREADS / 64];
+};
+
+// Floats of workspace one workgroup needs: A_0..A_n and D_0..D_n of a 64-row tile.
+static inline size_t stream_tile_floats(const MlpLayout &L) {
+  size_t s = 0;
+  for (int l = 0; l <= L.n_layers; ++l) s += (size_t)L.w[l];
+  return 2 * SROWS * s;
+}
+
+__device__ __forceinline__ const MlpLayout &stream_begin(StreamLds &S, const MlpLayout &Lk) {
+  const int *src = reinterpret_cast<const int *>(&Lk);
+  for (int i = threadIdx.x; i < (int)(sizeof(MlpLayout) / 4); i += blockDim.x) S.layout[i] = src[i];
+  if (threadIdx.x == 0) {
+    int s = 0;
+    for (int l = 0; l <= Lk.n_layers; ++l) {
+      S.pre[l] = s;
+      s += Lk.w[l];
+    }
+    S.pre[Lk.n_layers + 1] = s;
+  }
+  __syncthreads();
+  return *reinterpret_cast<const MlpLayout *>(S.layout);
+}
+
+// C[i][j] = init(i, j) + sum_{r < R} A(i, r) B(r, j) for i < M, j < N, handed to epi(i, j, value).
+//   A(i, r) = Ag[i * lda + r]  (A_T: Ag[r * lda + i]);   B(r, j) = Bg[r * ldb + j]  (B_T: Bg[j * ldb + r])
+// Called by the whole workgroup with the same arguments; ends with a barrier, after which what the
+// epilogues wrote is visible to every wave of the workgroup.
+template <bool A_T, bool B_T, typename Init, typename Epi>
+__device__ __forceinline__ void stream_gemm(StreamLds &S, const int M, const int N, const int R, const float *Ag,
+                                            const int lda, const float *Bg, const int ldb, Init init, Epi epi) {
+  const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63, m16 = lane & 15, q4 = lane >> 4;
+  constexpr int NA = SROWS * SKP / BORE_THREADS, NB = SKP * SNC / BORE_THREADS;
+  const int n_panels = (R + SKP - 1) / SKP;
+  for (int i0 = 0; i0 < M; i0 += SROWS)
+    for (int j0 = 0; j0 < N; j0 += SNC) {
+      float ra[NA], rb[NB];
+      auto fetch = [&](const int r0) {  // this work-item's share of the panels at r0: global -> registers
+#pragma unroll
+        for (int u = 0; u < NA; ++u) {
+          const int e = tid + BORE_THREADS * u;
+          const int i = i0 + (A_T ? (e & (SROWS - 1)) : e / SKP), r = r0 + (A_T ? e / SROWS : (e & (SKP - 1)));
+          ra[u] = (i < M && r < R) ? Ag[A_T ? r * lda + i : i * lda + r] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < NB; ++u) {
+          const int e = tid + BORE_THREADS * u;
+          const int j = j0 + (B_T ? e / SKP : (e & (SNC - 1))), r = r0 + (B_T ? (e & (SKP - 1)) : e / SNC);
+          rb[u] = (j < N && r < R) ? Bg[B_T ? j * ldb + r : r * ldb + j] : 0.f;
+        }
+      };
+      auto park = [&](const int buf) {  // registers -> LDS
+#pragma unroll
+        for (int u = 0; u < NA; ++u) {
+          const int e = tid + BORE_THREADS * u;
+          const int i = A_T ? (e & (SROWS - 1)) : e / SKP, r = A_T ? e / SROWS : (e & (SKP - 1));
+          S.a[buf][i * SLDA + r] = ra[u];
+        }
+#pragma unroll
+        for (int u = 0; u < NB; ++u) {
+          const int e = tid + BORE_THREADS * u;
+          const int j = B_T ? e / SKP : (e & (SNC - 1)), r = B_T ? (e & (SKP - 1)) : e / SNC;
+          S.b[buf][r * SLDB + j] = rb[u];
+        }
+      };
+      const int rows_here = min(SROWS, M - i0), ncb = (min(SNC, N - j0) + 15) >> 4;
+      const bool mine = 16 * wv < rows_here;  // (a wave without rows still stages panels and meets the barriers)
+      f32x4 acc[SNC / 16];
+#pragma unroll
+      for (int cb = 0; cb < SNC / 16; ++cb)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int i = i0 + 16 * wv + 4 * q4 + r, j = j0 + 16 * cb + m16;
+          acc[cb][r] = (mine && cb < ncb && i < M && j < N) ? init(i, j) : 0.f;
+        }
+      fetch(0);
+      park(0);
+      __syncthreads();
+      for (int p = 0; p < n_panels; ++p) {
+        const int buf = p & 1;
+        if (p + 1 < n_panels) fetch((p + 1) * SKP);
+        if (mine) {
+          const int kcs = (min(SKP, R - p * SKP) + 3) >> 2;
+          const float *ap = S.a[buf] + (16 * wv + m16) * SLDA + q4;
+          const float *bp = S.b[buf] + q4 * SLDB + m16;
+          for (int kc = 0; kc < kcs; ++kc) {
+            const float av = ap[4 * kc];
+#pragma unroll
+            for (int cb = 0; cb < SNC / 16; ++cb)
+              if (cb < ncb) acc[cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bp[4 * kc * SLDB + 16 * cb], acc[cb], 0, 0, 0);
+          }
+        }
+        if (p + 1 < n_panels) park(buf ^ 1);
+        __syncthreads();
+      }
+      if (mine) {
+#pragma unroll
+        for (int cb = 0; cb < SNC / 16; ++cb)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int i = i0 + 16 * wv + 4 * q4 + r, j = j0 + 16 * cb + m16;
+            if (cb < ncb && i < M && j < N) epi(i, j, acc[cb][r]);
+          }
+      }
+    }
+  __syncthreads();
+}
+
+// A_l = act_l(A_{l-1} W_l + b_l), l = 1..n, for the nr rows of the tile whose inputs sit in A_0.
+template <bool FIT>
+__device__ __forceinline__ void stream_forward(StreamLds &S, const MlpLayout &L, const float *th, float *ws, const int nr,
+                                               const bool keep_logits) {
+  const int n = L.n_layers;
+  for (int l = 1; l <= n; ++l) {
+    const int K = L.w[l - 1], Nw = L.w[l];
+    const float *Ain = ws + SROWS * S.pre[l - 1];
+    float *Aout = ws + SROWS * S.pre[l];
+    const float *bias = th + L.goff_b[l];
+    const int act = (keep_logits && l == n) ? (int)BORE_ACT_LINEAR : L.act[l];
+    stream_gemm<false, false>(
+        S, nr, Nw, K, Ain, K, th + L.goff_w[l], Nw, [](int, int) { return 0.f; },
+        [&](const int i, const int j, const float v) { Aout[i * Nw + j] = act_fwd<FIT>(act, v + bias[j]); });
+  }
+}
+
+// D_{l-1} = (D_l W_l^T) .* act'_{l-1}(A_{l-1}) for the nr rows of the tile (l == 1: no activation below).
+__device__ __forceinline__ void stream_backward_layer(StreamLds &S, const MlpLayout &L, const float *th, float *ws,
+                                                      const int nr, const int l) {
+  const int K = L.w[l - 1], Nw = L.w[l];
+  const float *Din = ws + SROWS * (S.pre[L.n_layers + 1] + S.pre[l]);
+  float *Dout = ws + SROWS * (S.pre[L.n_layers + 1] + S.pre[l - 1]);
+  const float *Aprev = ws + SROWS * S.pre[l - 1];
+  const int act = L.act[l - 1];
+  stream_gemm<false, true>(
+      S, nr, K, Nw, Din, Nw, th + L.goff_w[l], Nw, [](int, int) { return 0.f; },
+      [&](const int i, const int j, const float v) {
+        Dout[i * K + j] = l > 1 ? v * act_grad(act, Aprev[i * K + j]) : v;
+      });
+}
+
+// sum over l of l2_w[l] |W_l|^2 + l2_b[l] |b_l|^2: per-lane strided sums, a fixed tree over the lanes, then
+// the four waves in order.  Called by the whole workgroup after a barrier; every work-item gets the value.
+__device__ __forceinline__ float stream_penalty(StreamLds &S, const MlpLayout &L, const float *th) {
+  const int tid = threadIdx.x, nthr = blockDim.x;
+  float reg = 0.f;
+  for (int l = 1; l <= L.n_layers; ++l) {
+    const float lw = L.l2_w[l], lb = L.l2_b[l];
+    if (lw != 0.f)
+      for (int p = tid; p < L.w[l - 1] * L.w[l]; p += nthr) {
+        const float w = th[L.goff_w[l] + p];
+        reg = fmaf(lw * w, w, reg);
+      }
+    if (lb != 0.f)
+      for (int p = tid; p < L.w[l]; p += nthr) {
+        const float w = th[L.goff_b[l] + p];
+        reg = fmaf(lb * w, w, reg);
+      }
+  }
+  reg = wave_sum(reg);
+  if ((tid & 63) == 0) S.red[tid >> 6] = reg;
+  __syncthreads();
+  const float total = ((S.red[0] + S.red[1]) + S.red[2]) + S.red[3];
+  __syncthreads();
+  return total;
+}
+
+// ---------------------------------------------------------------------------
+// rows: forward, and value + input gradient.  Grid (model, row tiles).
+// ---------------------------------------------------------------------------
+struct StreamRowArgs {
+  MlpLayout L;
+  const float *theta;
+  const float *Xf;
+  const double *Xd;
+  float *out;
+  double *grad;
+  long long n_rows;
+  int x_shared, transform;
+  float sign;
+  float *ws;
+  long long ws_stride;  // floats per workgroup
+};
+
+template <bool WITH_GRAD>
+__global__ __launch_bounds__(BORE_THREADS) void stream_rows_kernel(const StreamRowArgs a) {
+  __shared__ StreamLds S;
+  const MlpLayout &L = stream_begin(S, a.L);
+  const int tid = threadIdx.x, nthr = blockDim.x;
+  const long long model = blockIdx.x;
+  const int n = L.n_layers, D = L.w[0];
+  const float *th = a.theta + model * L.P;
+  float *ws = a.ws + (model * gridDim.y + blockIdx.y) * a.ws_stride;
+  const long long xoff = a.x_shared ? 0 : model * a.n_rows * D;
+  float *out = a.out + model * a.n_rows;
+  const long long n_tiles = (a.n_rows + SROWS - 1) / SROWS;
+  float *A0 = ws, *An = ws + SROWS * S.pre[n];
+  for (long long t = blockIdx.y; t < n_tiles; t += gridDim.y) {
+    const long long row0 = t * SROWS;
+    const int nr = (int)min((long long)SROWS, a.n_rows - row0);
+    for (int i = tid; i < nr * D; i += nthr)
+      A0[i] = WITH_GRAD ? (float)a.Xd[xoff + row0 * D + i]  // Keras autocast fp64 -> fp32
+                        : a.Xf[xoff + row0 * D + i];
+    __syncthreads();
+    stream_forward<false>(S, L, th, ws, nr, false);
+    if constexpr (!WITH_GRAD) {
+      if (tid < nr) out[row0 + tid] = An[tid];
+    } else {
+      float *Dn = ws + SROWS * (S.pre[n + 1] + S.pre[n]);
+      if (tid < nr) {  // transforms and sign as fg_rowblock (mlp_device.h)
+        const float f = An[tid];
+        const float u = a.sign * f;
+        float T, dT;
+        if (a.transform == BORE_T_SIGMOID) {
+          T = sigmoid_stable(u);
+          dT = T * (1.f - T);
+        } else if (a.transform == BORE_T_EXP) {
+          T = expf(u);
+          dT = T;
+        } else {
+          T = u;
+          dT = 1.f;
+        }
+        out[row0 + tid] = T;
+        Dn[tid] = a.sign * dT * act_grad(L.act[n], f);
+      }
+      __syncthreads();
+      for (int l = n; l >= 1; --l) stream_backward_layer(S, L, th, ws, nr, l);
+      const float *D0 = ws + SROWS * S.pre[n + 1];
+      double *grad = a.grad + (model * a.n_rows + row0) * D;
+      for (int i = tid; i < nr * D; i += nthr) grad[i] = (double)D0[i];
+    }
+    __syncthreads();  // (the next tile overwrites the workspace)
+  }
+}
+
+// ---------------------------------------------------------------------------
+// evaluate: one workgroup per model over all N rows
+// ---------------------------------------------------------------------------
+struct StreamEvalArgs {
+  MlpLayout L;
+  const float *theta, *X, *z;
+  float *loss, *acc;
+  long long N;
+  float *ws;
+  long long ws_stride;
+};
+
+__global__ __launch_bounds__(BORE_THREADS) void stream_evaluate_kernel(const StreamEvalArgs a) {
+  __shared__ StreamLds S;
+  const MlpLayout &L = stream_begin(S, a.L);
+  const int tid = threadIdx.x, nthr = blockDim.x;
+  const long long model = blockIdx.x;
+  const int n = L.n_layers, D = L.w[0];
+  const float *th = a.theta + model * L.P;
+  float *ws = a.ws + model * a.ws_stride;
+  const float *X = a.X + model * a.N * D;
+  const float *z = a.z + model * a.N;
+  float *A0 = ws, *An = ws + SROWS * S.pre[n];
+  float lsum = 0.f, csum = 0.f;  // of this work-item's row slot, tile after tile
+  for (long long row0 = 0; row0 < a.N; row0 += SROWS) {
+    const int nr = (int)min((long long)SROWS, a.N - row0);
+    for (int i = tid; i < nr * D; i += nthr) A0[i] = X[row0 * D + i];
+    __syncthreads();
+    stream_forward<false>(S, L, th, ws, nr, true);
+    if (tid < nr) {  // loss and accuracy as evaluate_kernel defines them
+      const float x = An[tid];
+      const float zz = z[row0 + tid];
+      lsum += fmaxf(x, 0.f) - x * zz + log1pf(expf(-fabsf(x)));
+      const float o = L.act[n] == BORE_ACT_SIGMOID ? sigmoid_stable(x) : x;
+      csum += ((o > 0.5f) == (zz > 0.5f)) ? 1.f : 0.f;
+    }
+    __syncthreads();
+  }
+  const float reg = L.any_l2 ? stream_penalty(S, L, th) : 0.f;
+  lsum = wave_sum(lsum);  // (rows live in the first wave's slots only)
+  csum = wave_sum(csum);
+  if (tid == 0) {
+    a.loss[model] = lsum / (float)a.N + reg;
+    a.acc[model] = csum / (float)a.N;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// fit: ONE workgroup per model, every Adam step of the call in one launch
+// ---------------------------------------------------------------------------
+struct StreamFitArgs {
+  MlpLayout L;
+  float *theta, *am, *av;
+  long long *at;
+  const float *X, *z;
+  const int *perm;  // [models][epochs][N]: the caller's, or drawn by shuffle_kernel in front of this launch
+  float *epoch_loss;
+  int N, epochs, B;
+  float lr, beta1, beta2, eps;
+  float *ws;
+  long long ws_stride;  // floats per model: the tile's A / D, then (B > 64) the gradient sums [P]
+  long long o_g;
+};
+
+__global__ __launch_bounds__(BORE_THREADS) void stream_fit_kernel(const StreamFitArgs a) {
+  __shared__ StreamLds S;
+  const MlpLayout &L = stream_begin(S, a.L);
+  const int tid = threadIdx.x, nthr = blockDim.x;
+  const long long model = blockIdx.x;
+  const int n = L.n_layers, D = L.w[0], N = a.N, P = L.P;
+  float *th = a.theta + model * P, *mg = a.am + model * P, *vg = a.av + model * P;
+  const float *Xg = a.X + model * (long long)N * D;
+  const float *zg = a.z + model * (long long)N;
+  float *ws = a.ws + model * a.ws_stride;
+  float *gsum = ws + a.o_g;  // weight-gradient sums carried between the sub-tiles of a batch of more than 64 rows
+  float *A0 = ws, *An = ws + SROWS * S.pre[n];
+  float *Dn = ws + SROWS * (S.pre[n + 1] + S.pre[n]);
+
+  // running beta powers in fp64, rounded to fp32 at use (fit_body)
+  const long long t0 = a.at[model];
+  double b1p = pow((double)a.beta1, (double)t0);
+  double b2p = pow((double)a.beta2, (double)t0);
+  const float omb1 = 1.f - a.beta1, omb2 = 1.f - a.beta2;
+  const int steps = (N + a.B - 1) / a.B;
+  float reg = L.any_l2 ? stream_penalty(S, L, th) : 0.f;  // penalty of the weights the next step's loss sees
+
+  for (int e = 0; e < a.epochs; ++e) {
+    const int *perm = a.perm + (model * a.epochs + e) * (long long)N;
+    float eloss = 0.f;  // of this work-item's row slot
+    float ereg = 0.f;   // penalty x rows, step after step (the same in every work-item)
+    for (int s = 0; s < steps; ++s) {
+      const int row0 = s * a.B;
+      const int nb = min(a.B, N - row0);
+      const float inv_nb = fit_rcp((float)nb);
+      b1p *= (double)a.beta1;
+      b2p *= (double)a.beta2;
+      const float alpha = a.lr * sqrtf(1.f - (float)b2p) / (1.f - (float)b1p);
+      if (L.any_l2) ereg += reg * (float)nb;
+      const int nsub = (nb + SROWS - 1) / SROWS;
+      for (int sub = 0; sub < nsub; ++sub) {
+        const int r0 = row0 + sub * SROWS;
+        const int nr = min(SROWS, nb - sub * SROWS);
+        const bool first_sub = sub == 0, last_sub = sub + 1 == nsub;
+        // ---- gather, forward, loss ----
+        for (int i = tid; i < nr * D; i += nthr) {
+          const int r = i / D, d = i - r * D;
+          A0[i] = Xg[(long long)perm[r0 + r] * D + d];
+        }
+        if (tid < nr) S.zt[tid] = zg[perm[r0 + tid]];
+        __syncthreads();
+        stream_forward<true>(S, L, th, ws, nr, true);
+        if (tid < nr) {  // BCE from logits and d loss / d logit, as fit_body
+          const float x = An[tid];
+          const float zz = S.zt[tid];
+          const float ex = fit_exp_neg(-fabsf(x));
+          const float rden = fit_rcp(1.f + ex);
+          const float sig = x >= 0.f ? rden : ex * rden;
+          eloss += fmaxf(x, 0.f) - x * zz + log1pf(ex);
+          Dn[tid] = (sig - zz) * inv_nb;
+        }
+        __syncthreads();
+        // ---- per layer, descending: D_{l-1} from the OLD W_l, then dW_l = A_{l-1}^T D_l and its Adam update ----
+        for (int l = n; l >= 1; --l) {
+          if (l > 1) stream_backward_layer(S, L, th, ws, nr, l);
+          const int K = L.w[l - 1], Nw = L.w[l];
+          const float *Aprev = ws + SROWS * S.pre[l - 1];
+          const float *Dl = ws + SROWS * (S.pre[n + 1] + S.pre[l]);
+          const int gw = L.goff_w[l], gb = L.goff_b[l];
+          const float l2w = L.l2_w[l], l2b = L.l2_b[l];
+          stream_gemm<true, false>(
+              S, K, Nw, nr, Aprev, K, Dl, Nw,
+              [&](const int i, const int j) { return first_sub ? 0.f : gsum[gw + i * Nw + j]; },
+              [&](const int i, const int j, const float v) {
+                const int p = gw + i * Nw + j;
+                if (!last_sub) {
+                  gsum[p] = v;
+                  return;
+                }
+                const float w = th[p];
+                float g = v, mm = mg[p], vv = vg[p];
+                if (l2w != 0.f) g = fmaf(2.f * l2w, w, g);
+                th[p] = adam_update(w, g, mm, vv, alpha, omb1, omb2, a.eps);
+                mg[p] = mm;
+                vg[p] = vv;
+              });
+          for (int j = tid; j < Nw; j += nthr) {  // bias gradient: the column sums of D_l, rows in ascending order
+            float g = first_sub ? 0.f : gsum[gb + j];
+            for (int r = 0; r < nr; ++r) g += Dl[r * Nw + j];
+            if (!last_sub) {
+              gsum[gb + j] = g;
+              continue;
+            }
+            const float w = th[gb + j];
+            float mm = mg[gb + j], vv = vg[gb + j];
+            if (l2b != 0.f) g = fmaf(2.f * l2b, w, g);
+            th[gb + j] = adam_update(w, g, mm, vv, alpha, omb1, omb2, a.eps);
+            mg[gb + j] = mm;
+            vg[gb + j] = vv;
+          }
+        }
+        __syncthreads();  // the step's theta (and the sub-tile's sums) before anybody reads them
+      }
+      if (L.any_l2) reg = stream_penalty(S, L, th);
+    }
+    if (a.epoch_loss) {
+      eloss = wave_sum(eloss);  // (rows live in the first wave's slots only)
+      if (tid == 0) a.epoch_loss[model * a.epochs + e] = (eloss + ereg) / (float)N;
+    }
+  }
+  if (tid == 0) a.at[model] = t0 + (long long)a.epochs * steps;
+}
+
+}  // namespace bore
+
+// ---------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------
+using namespace bore;
+
+// Within the streamed flavour's bounds?  A predicate: leaves the thread's error string alone.
+static bool stream_within_bounds(const bore_mlp_desc *desc) {
+  MlpLayout L;
+  if (bore_make_layout(desc, 0, BORE_BATCH_MAX, &L) || desc->compute != BORE_COMPUTE_F32) return false;
+  for (int l = 0; l <= L.n_layers; ++l)
+    if (L.w[l] > BORE_STREAM_MAX_UNITS) return false;
+  return true;
+}
+
+// The same as a check: 0, or the error (BORE_E_UNSUPPORTED names the bound).
+static int stream_bounds(const bore_mlp_desc *desc, MlpLayout *L) {
+  if (bore_make_layout(desc, 0, BORE_BATCH_MAX, L)) return fail(BORE_E_INVALID, "bad bore_mlp_desc");
+  if (desc->compute != BORE_COMPUTE_F32) return fail(BORE_E_UNSUPPORTED, kBf16Shapes);
+  for (int l = 0; l <= L->n_layers; ++l)
+    if (L->w[l] > BORE_STREAM_MAX_UNITS)
+      return fail(BORE_E_UNSUPPORTED,
+                  "the model does not fit one workgroup's LDS and %s %d exceeds what the streamed kernels take "
+                  "(BORE_STREAM_MAX_UNITS = %d)",
+                  l ? "a layer width of" : "an input dimension of", L->w[l], BORE_STREAM_MAX_UNITS);
+  return 0;
+}
+
+// BORE_STREAM = 1 (tests, A/B): any float32 request within the bounds takes the streamed flavour.
+static bool stream_forced(const bore_mlp_desc *desc) {
+  const char *env = getenv("BORE_STREAM");
+  if (!env || !atoi(env) || !desc || g_batch) return false;
+  return stream_within_bounds(desc);
+}
+
+static int stream_rows(bool with_grad, const bore_mlp_desc *desc, int n_models, const float *theta, const float *Xf,
+                       const double *Xd, int64_t n_rows, int x_shared, int transform, float sign, float *out,
+                       double *grad, void *stream) {
+  StreamRowArgs a;
+  if (const int rc = stream_bounds(desc, &a.L)) return rc;
+  if (n_models < 1) return fail(BORE_E_INVALID, "n_models must be >= 1 (got %d)", n_models);
+  if (a.L.w[a.L.n_layers] != 1) return fail(BORE_E_INVALID, "the last Dense layer must have 1 unit");
+  if (!theta || !(with_grad ? (const void *)Xd : (const void *)Xf) || !out || (with_grad && !grad))
+    return fail(BORE_E_INVALID, "null pointer");
+  if (n_rows < 0) return fail(BORE_E_INVALID, "n_rows < 0");
+  if (n_rows == 0) return 0;
+  a.theta = theta; a.Xf = Xf; a.Xd = Xd; a.out = out; a.grad = grad;
+  a.n_rows = n_rows; a.x_shared = x_shared; a.transform = transform; a.sign = sign;
+  // two workgroups per CU's worth of tiles in flight, never more than there is work, and never more than
+  // STREAM_WS_BYTES of workspace per call (a workgroup walks several tiles then): 64 MiB is 512 workgroups at
+  // 8->256-256-1 and 32 at eight layers of 512
+  a.ws_stride = (long long)stream_tile_floats(a.L);
+  long long gy = (n_rows + SROWS - 1) / SROWS;
+  const long long cap = (2 * device_cus() + n_models - 1) / n_models;
+  if (gy > cap) gy = cap;
+  const long long by_bytes = STREAM_WS_BYTES / ((long long)n_models * a.ws_stride * (long long)sizeof(float));
+  if (gy > by_bytes) gy = by_bytes;
+  if (gy > 65535) gy = 65535;
+  if (gy < 1) gy = 1;
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipMallocAsync((void **)&a.ws, (size_t)n_models * gy * a.ws_stride * sizeof(float), st));
+  const dim3 grid(n_models, (unsigned)gy);
+  if (with_grad) hipLaunchKernelGGL(stream_rows_kernel<true>, grid, dim3(BORE_THREADS), 0, st, a);
+  else hipLaunchKernelGGL(stream_rows_kernel<false>, grid, dim3(BORE_THREADS), 0, st, a);
+  const hipError_t e = hipGetLastError();
+  (void)hipFreeAsync(a.ws, st);
+  if (e != hipSuccess) return fail(BORE_E_HIP, "streamed rows kernel: %s", hipGetErrorString(e));
+  return 0;
+}
+
+static int stream_forward_entry(const bore_mlp_desc *desc, int n_models, const float *theta, const float *X,
+                                int64_t n_rows, int x_shared, float *out, void *stream) {
+  return stream_rows(false, desc, n_models, theta, X, nullptr, n_rows, x_shared, 0, 1.f, out, nullptr, stream);
+}
+
+static int stream_value_and_input_grad(const bore_mlp_desc *desc, int n_models, const float *theta, const double *X,
+                                       int64_t n_rows, int transform, int negate, float *val, double *grad,
+                                       void *stream) {
+  if (transform < BORE_T_IDENTITY || transform > BORE_T_EXP)
+    return fail(BORE_E_INVALID, "value_and_input_grad: unknown transform %d", transform);
+  return stream_rows(true, desc, n_models, theta, nullptr, X, n_rows, 0, transform, negate ? -1.f : 1.f, val, grad,
+                     stream);
+}
+
+static int stream_evaluate(const bore_mlp_desc *desc, int n_models, const float *theta, const float *X, const float *z,
+                           int64_t N, float *loss, float *acc, void *stream) {
+  StreamEvalArgs a;
+  if (const int rc = stream_bounds(desc, &a.L)) return rc;
+  if (n_models < 1) return fail(BORE_E_INVALID, "n_models must be >= 1 (got %d)", n_models);
+  if (a.L.w[a.L.n_layers] != 1) return fail(BORE_E_INVALID, "evaluate: the last Dense layer must have 1 unit");
+  if (!theta || !X || !z || !loss || !acc) return fail(BORE_E_INVALID, "evaluate: null pointer");
+  if (N < 1) return fail(BORE_E_INVALID, "evaluate: N < 1");
+  a.theta = theta; a.X = X; a.z = z; a.loss = loss; a.acc = acc; a.N = N;
+  a.ws_stride = (long long)stream_tile_floats(a.L);
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipMallocAsync((void **)&a.ws, (size_t)n_models * a.ws_stride * sizeof(float), st));
+  hipLaunchKernelGGL(stream_evaluate_kernel, dim3(n_models), dim3(BORE_THREADS), 0, st, a);
+  const hipError_t e = hipGetLastError();
+  (void)hipFreeAsync(a.ws, st);
+  if (e != hipSuccess) return fail(BORE_E_HIP, "streamed evaluate kernel: %s", hipGetErrorString(e));
+  return 0;
+}
+
+static int stream_fit(const bore_mlp_desc *desc, int n_models, float *theta, float *adam_m, float *adam_v,
+                      int64_t *adam_t, const float *X, const float *z, int64_t N, int epochs, int batch_size,
+                      const int32_t *perm, uint64_t seed, int64_t model_index0, int64_t epoch0,
+                      const bore_adam_cfg *adam, float *epoch_loss, void *stream) {
+  StreamFitArgs a;
+  if (const int rc = stream_bounds(desc, &a.L)) return rc;
+  if (n_models < 1) return fail(BORE_E_INVALID, "n_models must be >= 1 (got %d)", n_models);
+  if (batch_size < 1) return fail(BORE_E_INVALID, "fit: batch_size must be positive (got %d)", batch_size);
+  if (N < 1 || N > (1 << 24)) return fail(BORE_E_INVALID, "fit: N=%lld out of range", (long long)N);
+  const MlpLayout &L = a.L;
+  if (L.w[L.n_layers] != 1)
+    return fail(BORE_E_INVALID, "fit: the last Dense layer must have 1 unit (binary classifier)");
+  if (L.act[L.n_layers] != BORE_ACT_SIGMOID && L.act[L.n_layers] != BORE_ACT_LINEAR)
+    return fail(BORE_E_INVALID, "fit: BCE needs a sigmoid or linear (from_logits) output layer");
+  if (!theta || !adam_m || !adam_v || !adam_t || !X || !z || !adam) return fail(BORE_E_INVALID, "fit: null pointer");
+  if (epochs < 0) return fail(BORE_E_INVALID, "fit: epochs < 0");
+  if (epochs == 0) return 0;
+  // the call's shuffles, when the caller passes none: the project's one stream (shuffle_kernel), drawn into the
+  // scratch in front of the fit on the same stream
+  const size_t perm_ints = perm ? 0 : (size_t)n_models * epochs * N;
+  // (as long as shuffle_kernel can rank N rows in LDS and the call's shuffles take no more than STREAM_WS_BYTES;
+  // beyond: the caller's turn, which bore_amd.models takes a few epochs per launch)
+  if (!perm && (epochs > 65535 || (size_t)perm_scratch_floats(N) * 4 > BORE_LDS_BYTES ||
+                perm_ints * sizeof(int32_t) > (size_t)STREAM_WS_BYTES))
+    return fail(BORE_E_NEEDS_PERM,
+                "fit: the shuffles of %d models x %d epochs x N=%lld rows are not drawn on the device (more rows than "
+                "an LDS ranks, or more than %lld MiB of them): pass explicit shuffles (`perm`, e.g. from "
+                "bore_amd.shuffle.permutations) -- any N then",
+                n_models, epochs, (long long)N, STREAM_WS_BYTES >> 20);
+  a.theta = theta; a.am = adam_m; a.av = adam_v; a.at = (long long *)adam_t;
+  a.X = X; a.z = z; a.epoch_loss = epoch_loss;
+  a.N = (int)N; a.epochs = epochs; a.B = batch_size;
+  a.lr = adam->lr; a.beta1 = adam->beta1; a.beta2 = adam->beta2; a.eps = adam->eps;
+  a.o_g = (long long)stream_tile_floats(L);
+  a.ws_stride = a.o_g + (batch_size > BORE_BATCH_MAX ? L.P : 0);
+  hipStream_t st = (hipStream_t)stream;
+  const size_t ws_floats = (size_t)n_models * a.ws_stride;
+  float *buf = nullptr;
+  HIP_TRY(hipMallocAsync((void **)&buf, (ws_floats + perm_ints) * sizeof(float), st));
+  a.ws = buf;
+  a.perm = perm;
+  int rc = 0;
+  if (!perm) {
+    int32_t *drawn = reinterpret_cast<int32_t *>(buf + ws_floats);
+    rc = bore_shuffle_perm(seed, model_index0, n_models, epoch0, epochs, N, drawn, stream);
+    a.perm = drawn;
+  }
+  if (rc == 0) {
+    hipLaunchKernelGGL(stream_fit_kernel, dim3(n_models), dim3(BORE_THREADS), 0, st, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) rc = fail(BORE_E_HIP, "streamed fit kernel: %s", hipGetErrorString(e));
+  }
+  (void)hipFreeAsync(buf, st);
+  return rc;
+}
+
+extern "C" int bore_mlp_streamed(const bore_mlp_desc *desc) {
+  MlpLayout L;
+  if (bore_make_layout(desc, 0, BORE_BATCH_MAX, &L)) return fail(BORE_E_INVALID, "bad bore_mlp_desc");
+  if (desc->compute != BORE_COMPUTE_F32) return 0;  // (bfloat16: the wide static shapes, never streamed)
+  const bore_batch *batch = g_batch;
+  g_batch = nullptr;  // (the plain entry points' checks)
+  int mask = 0;
+  if (check_common(desc, 1, 0, BORE_BATCH_MAX, true, BORE_BATCH_MAX + BORE_LAYOUT_FLOATS + 4, &L) == BORE_E_UNSUPPORTED)
+    mask |= 1;
+  if (check_common(desc, 1, 2, BORE_BATCH_MAX, true, BORE_BATCH_MAX + BORE_LAYOUT_FLOATS + 4, &L) == BORE_E_UNSUPPORTED)
+    mask |= 2;
+  {  // (the fit's own check at one row and 64-row batches; it stops at the null pointers when the network fits)
+    FitArgs probe;
+    size_t off = 0;
+    int shape = 0;
+    if (fit_build(desc, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 1, BORE_BATCH_MAX, nullptr, 0, 0, 0,
+                  nullptr, nullptr, probe, off, shape) == BORE_E_UNSUPPORTED)
+      mask |= 4;
+  }
+  g_batch = batch;
+  g_bore_err[0] = 0;
+  if (mask)  // (refused by the LDS flavours: inside the streamed flavour's bounds, or the bound by name)
+    if (const int rc = stream_bounds(desc, &L)) return rc;
+  return mask;
+}

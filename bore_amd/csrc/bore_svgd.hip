@@ -481,8 +481,8 @@ extern "C" int bore_svgd_optimize(const bore_mlp_desc *desc, int n_models, const
   off = (off + 3) & ~(size_t)3;
   a.o_layout = (int)off; off += BORE_LAYOUT_FLOATS;
   if (off * 4 > BORE_LDS_BYTES)
-    return fail(BORE_E_UNSUPPORTED, "svgd_optimize: %d particles in %d dimensions need %zu B of LDS (> %d)",
-                n, D, off * 4, BORE_LDS_BYTES);
+    return fail(BORE_E_UNSUPPORTED, "svgd_optimize: %d particles in %d dimensions need %zu B of LDS (> %d) beside the network; %s",
+                n, D, off * 4, BORE_LDS_BYTES, kStreamedElsewhere);
   auto launch = [&](auto BF) {  // (BF: 0 = a float32 network, 3 / 4 = the bfloat16 image of that wide shape)
     if (big) return launch_lds(svgd_big_kernel<BF()>, dim3(n_models), dim3(BORE_THREADS), off * 4, stream, a);
     return launch_lds(svgd_kernel<BF()>, dim3(n_models), dim3(BORE_THREADS), off * 4, stream, a);

@@ -28,14 +28,20 @@ inline int fail(int code, const char *fmt, ...) {
     if (e_ != hipSuccess) return fail(BORE_E_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
   } while (0)
 
+// What the entry points WITHOUT a streamed flavour (bore_stream.hip) tell the owner of a network too large for LDS.
+static const char kStreamedElsewhere[] =
+    "this entry point keeps the whole network in LDS -- forward, evaluate, value + input gradient and fit stream "
+    "such float32 networks from global memory, and the model API runs their restarts through the lock-step "
+    "L-BFGS-B around the streamed kernels";
+
 // Raise the kernel's dynamic-LDS limit to `bytes` (default cap is 64 KiB).
 // The attribute only ever needs to grow: one runtime call per kernel per new high-water mark
 // (hipFuncSetAttribute is a driver round trip -- not something for every launch).
 template <typename K>
 inline int allow_lds(K kernel, size_t bytes) {
   if (bytes > BORE_LDS_BYTES)
-    return fail(BORE_E_UNSUPPORTED, "model needs %zu B of LDS per workgroup (> %d)", bytes,
-                BORE_LDS_BYTES);
+    return fail(BORE_E_UNSUPPORTED, "model needs %zu B of LDS per workgroup (> %d); %s", bytes,
+                BORE_LDS_BYTES, kStreamedElsewhere);
   // the attribute is per device; callers on different host threads (ctypes releases the GIL)
   // share this table
   struct Seen { const void *k; int dev; size_t bytes; };
@@ -153,7 +159,7 @@ inline int check_common(const bore_mlp_desc *desc, int n_models, int with_deltas
     if (need <= BORE_LDS_BYTES) return 0;
     if (!may_shrink || tb <= 16)
       return fail(BORE_E_UNSUPPORTED,
-                  "model needs %zu B of LDS per workgroup (> %d) at %d rows per tile", need,
-                  BORE_LDS_BYTES, tb);
+                  "model needs %zu B of LDS per workgroup (> %d) at %d rows per tile; %s", need,
+                  BORE_LDS_BYTES, tb, kStreamedElsewhere);
   }
 }

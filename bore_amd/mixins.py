@@ -161,9 +161,25 @@ class MaximizableMixin:
         x, fun, jac, info = (t[0] for t in ops.lbfgsb_results_to_host(x, fun, jac, info))
         return f_init, self._results(x, fun, jac, info, [where[int(r)] for r in order])
 
+    def _streamed(self, x=None):
+        """Does value + input gradient of this model run on the streamed kernels (a float32 network too large for
+        one workgroup's LDS, ``ops.mlp_streamed``)?  The in-kernel screening and restarts keep the network in LDS,
+        so for such a model screening is ``predict`` + ``argpartition`` and the restarts are the lock-step L-BFGS-B
+        around the streamed f/g kernel: its designed route, no warning."""
+        from . import _lib, ops
+        if getattr(self, "_desc", None) is None and x is not None and hasattr(self, "_ensure_built"):
+            self._ensure_built(x)
+        desc = getattr(self, "_desc", None)
+        if not isinstance(desc, _lib.MlpDesc):              # (not a Dense stack)
+            return False
+        seen = getattr(self, "_streamed_seen", None)
+        if seen is None or seen[0] is not desc:             # (asked once per built network)
+            seen = self._streamed_seen = (desc, bool(ops.mlp_streamed(desc) & 2))
+        return seen[1]
+
     def _minimize_from(self, X0, bounds, method, options):
         assert self.restart_mode in RESTART_MODES, self.restart_mode
-        if method == "L-BFGS-B" and self.restart_mode == "device":
+        if method == "L-BFGS-B" and self.restart_mode == "device" and not self._streamed(X0):
             from ._lib import UnsupportedError
             try:
                 if self._func_min.transform.name is None:
@@ -192,7 +208,7 @@ class MaximizableMixin:
         X_init = random_state.uniform(low=low, high=high, size=(num_samples, dim))    # (ONE draw, bore/mixins.py:45-47)
         f_init = results = None
         if (self.screen_mode == "device" and self.restart_mode == "device" and method == "L-BFGS-B" and num_starts > 0
-                and self._func_min.transform.name is not None):
+                and self._func_min.transform.name is not None and not self._streamed(X_init)):
             from ._lib import UnsupportedError
             try:
                 f_init, results = self._maxima_on_device(X_init, bounds, num_starts, dict(options or {}))

@@ -34,6 +34,16 @@ def param_count(desc):
     return int(p)
 
 
+def mlp_streamed(desc):
+    """Which entry points run ``desc`` on the streamed flavour (parameters in global memory, for networks too large
+    for one workgroup's LDS): bit 0 forward / evaluate, bit 1 value + input gradient, bit 2 fit.  A host query;
+    raises ``UnsupportedError`` naming the bound for a network that fits neither flavour."""
+    mask = int(_lib.lib().bore_mlp_streamed(C.byref(desc)))
+    if mask < 0:
+        _lib.check(mask)
+    return mask
+
+
 def mlp_forward(desc, theta, X, out=None):
     """theta [L,P] f32; X [L,N,D] f32 or [N,D] f32 shared by all models -> [L,N] f32."""
     L, P = theta.shape

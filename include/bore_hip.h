@@ -559,6 +559,34 @@ int bore_lstm_evaluate(const bore_lstm_desc *desc, int n_models, const float *th
                        const float *y, int64_t N, int T, float mask_value, float *loss, float *acc,
                        void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Streamed flavour: float32 Dense stacks whose parameters do not fit one workgroup's LDS.  The
+ * parameters stay in global memory (L2-resident in practice) and pass through LDS in panels;
+ * bore_mlp_forward, bore_mlp_evaluate, bore_mlp_value_and_input_grad and bore_mlp_fit take this
+ * flavour exactly when their own LDS check refuses the network, so nothing that ran before changes
+ * route.  The environment variable BORE_STREAM=1 (read on every call) forces it for any float32
+ * request within the bounds (tests, A/B).  Bounds: every width and the input dimension
+ * <= BORE_STREAM_MAX_UNITS, up to BORE_MAX_LAYERS layers, any activations, l2, batch_size and N;
+ * BORE_E_UNSUPPORTED names the bound otherwise.  bore_mlp_fit also comes here for a network that fits LDS when
+ * the REQUEST does not -- every BORE_E_UNSUPPORTED of its LDS carve: 32->128-128-1 with more rows than its in-LDS
+ * shuffle holds, the gradient sums of a batch_size above 64 beside a large network, a wide static shape with an
+ * explicit perm too long for LDS -- which bore_mlp_streamed, a query about the network alone, does not report.
+ * Workspace per call, stream-ordered: the rows kernels at most 64 MiB (or one 64-row tile per model), the fit
+ * 2*64*sum(widths) + (batch_size > 64: P) floats per model, plus, with perm == NULL, the drawn shuffles
+ * (n_models*epochs*N ints, at most 64 MiB: BORE_E_NEEDS_PERM beyond, as for N too long to rank in LDS).  One workgroup per model in the fit: a single
+ * model leaves the rest of the device idle.  The screening, restart, SVGD and engine entry points
+ * keep the network in LDS and keep refusing such networks.  Additive to ABI 12.
+ * --------------------------------------------------------------------------------------------- */
+#define BORE_STREAM_MAX_UNITS 512
+
+/* Pure host query (ignores BORE_STREAM): which entry points would run `desc` streamed.
+ *   bit 0  bore_mlp_forward / bore_mlp_evaluate
+ *   bit 1  bore_mlp_value_and_input_grad
+ *   bit 2  bore_mlp_fit with 64-row batches
+ * 0 for a network that fits LDS and for bfloat16; BORE_E_INVALID on a bad descriptor;
+ * BORE_E_UNSUPPORTED (the bound named) for a network that fits neither. */
+int bore_mlp_streamed(const bore_mlp_desc *desc);
+
 #ifdef __cplusplus
 }
 #endif
