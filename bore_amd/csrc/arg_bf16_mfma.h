@@ -343,6 +343,8 @@ struct ArgBf16Net {
     predict(im, xf);
     const float f = out;
     const float u = sign * f;
+    // objective_transform (mlp_math.h) written out: inlined from the helper, the two values reach this flavour's
+    // kernels in the other order and their registers are named differently (same values)
     float Tv, dT;
     if (transform == BORE_T_SIGMOID) {
       Tv = sigmoid_stable(u);

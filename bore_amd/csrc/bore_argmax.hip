@@ -1133,8 +1133,7 @@ static int lbfgsb_build(const bore_mlp_desc *desc, int n_models, const float *th
   if (D < 1 || D > BORE_DIM_MAX)
     return fail(BORE_E_UNSUPPORTED, "lbfgsb_minimize: input_dim must be 1..%d", BORE_DIM_MAX);
   if (num_starts < 1) return fail(BORE_E_INVALID, "lbfgsb_minimize: num_starts < 1");
-  if (transform < BORE_T_IDENTITY || transform > BORE_T_EXP)
-    return fail(BORE_E_INVALID, "lbfgsb_minimize: unknown transform %d", transform);
+  if (const int rc = check_transform("lbfgsb_minimize", transform)) return rc;
   if (opts->maxcor < 1 || opts->maxcor > 32)
     return fail(BORE_E_UNSUPPORTED, "lbfgsb_minimize: maxcor must be 1..32");
   if (opts->maxls < 1) return fail(BORE_E_INVALID, "lbfgsb_minimize: maxls must be positive.");

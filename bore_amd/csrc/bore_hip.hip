@@ -145,23 +145,6 @@ struct FitArgs {
   long long cap;
 };
 
-// The fit's arithmetic is "at most 1 ulp per operation", not IEEE-correctly-rounded: square root,
-// reciprocal and exp2 are the hardware's v_sqrt_f32 / v_rcp_f32 / v_exp_f32 (1 ulp each).  TensorFlow's
-// own Eigen kernels are not correctly rounded either; the parity gate is the oracle
-// tolerance of tests/test_gpu_parity.py, not the bits of a previous build.  The correctly rounded forms
-// (ocml expf, IEEE division and sqrt: ~30 dependent instructions per updated register) were 0.8 - 1.2 k
-// cycles of a 3.3 - 3.7 k-cycle Adam step (profiles/r3/fit_marks_final.txt).  The L-BFGS-B (fp64,
-// lbfgsb.h) and the objective evaluation keep their IEEE forms.
-// (fit_rcp, fit_sqrt, fit_exp_neg, fit_elu: mlp_device.h -- the register network of mlp_regs.h uses them too)
-
-// Adam update of one parameter (ResourceApplyAdam, non-nesterov); returns the new weight.
-__device__ __forceinline__ float adam_update(float w, float g, float &m, float &v, float alpha,
-                                             float omb1, float omb2, float eps) {
-  m += (g - m) * omb1;
-  v += (g * g - v) * omb2;
-  return fmaf(-(m * alpha), fit_rcp(fit_sqrt(v) + eps), w);
-}
-
 // Weight gradients + Adam for a static shape, NBLK = row-blocks of the batch that hold live
 // rows (the other blocks' rows are never read).  Same sums as the generic loop in fit_kernel
 // (k-ordered over the batch rows), but with every trip count a constant: the 2 x 4 NBLK MFMA
@@ -968,10 +951,8 @@ __device__ __forceinline__ void fit_body(const FitArgs &a, const long long slot,
     if (lane == 0) atomicAdd(&misc[0], reg);
   }
 
-  // running beta powers in fp64 (rounded to fp32 at use; see DESIGN.md "Adam")
   const long long t0 = a.at[model];
-  double b1p = pow((double)a.beta1, (double)t0);
-  double b2p = pow((double)a.beta2, (double)t0);
+  AdamClock clock(a.beta1, a.beta2, t0);
   const float omb1 = 1.f - a.beta1, omb2 = 1.f - a.beta2;
   const int steps = (N + a.B - 1) / a.B;
   // Shuffles and row gathers off the step chain: when the LAST step of an epoch leaves the fourth wave
@@ -1021,9 +1002,7 @@ __device__ __forceinline__ void fit_body(const FitArgs &a, const long long slot,
   // first one; after that the last wave computes the NEXT step's while it waits at the end of
   // the weight-gradient phase and leaves it in misc[5] (one sqrt + divide per step per
   // workgroup instead of per wave, and off the step's critical path).
-  b1p *= (double)a.beta1;
-  b2p *= (double)a.beta2;
-  const float alpha_first = a.lr * sqrtf(1.f - (float)b2p) / (1.f - (float)b1p);
+  const float alpha_first = clock.advance(a.lr, a.beta1, a.beta2);
   bool first_step = true;
   __syncthreads();
 #ifdef BORE_FIT_MARKS
@@ -1182,11 +1161,7 @@ __device__ __forceinline__ void fit_body(const FitArgs &a, const long long slot,
           float delta = 0.f;
           if (lane < 16 && live) {
             const float x = net.h[Net::n][0][0];
-            const float ex = fit_exp_neg(-fabsf(x));
-            const float rden = fit_rcp(1.f + ex);
-            const float sig = x >= 0.f ? rden : ex * rden;
-            if (a.epoch_loss) eloss += fmaxf(x, 0.f) - x * zz + log1pf(ex);
-            delta = (sig - zz) * inv_nb;
+            delta = fit_bce(x, zz, a.epoch_loss != nullptr, eloss) * inv_nb;
           }
           if (lane < 16) {
             if constexpr (ROUNDS) {
@@ -1240,12 +1215,7 @@ __device__ __forceinline__ void fit_body(const FitArgs &a, const long long slot,
           if (row < nr) {
             const float x = tile[L.aoff[n] + row * L.lda[n]];
             const float zz = zt[row];
-            const float ex = fit_exp_neg(-fabsf(x));  // shared by the loss and the sigmoid
-            const float rden = fit_rcp(1.f + ex);
-            const float sig = x >= 0.f ? rden : ex * rden;
-            if (a.epoch_loss)  // per-lane; reduced once per epoch
-              eloss += fmaxf(x, 0.f) - x * zz + log1pf(ex);
-            delta = (sig - zz) * inv_nb;
+            delta = fit_bce(x, zz, a.epoch_loss != nullptr, eloss) * inv_nb;  // (eloss: per lane, reduced once per epoch)
           }
           tile[L.doff[n] + row * L.lda[n]] = delta;
         }
@@ -1447,9 +1417,7 @@ __device__ __forceinline__ void fit_body(const FitArgs &a, const long long slot,
         if (lane == 0) atomicAdd(&misc[0], reg);
       }
       if (wv == (BORE_THREADS / 64) - 1) {  // the next step's size (read after the barrier below)
-        b1p *= (double)a.beta1;
-        b2p *= (double)a.beta2;
-        const float an = a.lr * sqrtf(1.f - (float)b2p) / (1.f - (float)b1p);
+        const float an = clock.advance(a.lr, a.beta1, a.beta2);
         if (lane == 0) misc[5] = an;
       }
       BORE_STAMP(6);
@@ -1561,13 +1529,10 @@ __global__ __launch_bounds__(BORE_THREADS) void fit_bf16_kernel(const FitBf16Arg
   for (int p = tid; p < P; p += nthr) th16[param_ref(L, p, n).lds] = f32_to_bf16(theta_g[p]);
 
   const long long t0 = a.at[model];
-  double b1p = pow((double)a.beta1, (double)t0);
-  double b2p = pow((double)a.beta2, (double)t0);
+  AdamClock clock(a.beta1, a.beta2, t0);
   const float omb1 = 1.f - a.beta1, omb2 = 1.f - a.beta2;
   const int steps = (N + a.B - 1) / a.B;
-  b1p *= (double)a.beta1;
-  b2p *= (double)a.beta2;
-  const float alpha_first = a.lr * sqrtf(1.f - (float)b2p) / (1.f - (float)b1p);
+  const float alpha_first = clock.advance(a.lr, a.beta1, a.beta2);
   bool first_step = true;
   __syncthreads();
 #ifdef BORE_FIT_MARKS
@@ -1622,11 +1587,7 @@ __global__ __launch_bounds__(BORE_THREADS) void fit_bf16_kernel(const FitBf16Arg
         float delta = 0.f;
         if (lane < 16 && live) {
           const float x = net.h[n][0][0];
-          const float ex = fit_exp_neg(-fabsf(x));
-          const float rden = fit_rcp(1.f + ex);
-          const float sig = x >= 0.f ? rden : ex * rden;
-          if (a.epoch_loss) eloss += fmaxf(x, 0.f) - x * zz + log1pf(ex);
-          delta = bf16_round((sig - zz) * inv_nb);
+          delta = bf16_round(fit_bce(x, zz, a.epoch_loss != nullptr, eloss) * inv_nb);
         }
         if (lane < 16) tile16[L.doff[n] + row * L.lda[n]] = f32_to_bf16(delta);
         net.set_output_delta(delta);
@@ -1658,9 +1619,7 @@ __global__ __launch_bounds__(BORE_THREADS) void fit_bf16_kernel(const FitBf16Arg
         for (int i = tid; i < BORE_BATCH_MAX * L.lda[n]; i += nthr) tile16[L.doff[n] + i] = 0;
       }
       if (wv == (BORE_THREADS / 64) - 1) {
-        b1p *= (double)a.beta1;
-        b2p *= (double)a.beta2;
-        const float an = a.lr * sqrtf(1.f - (float)b2p) / (1.f - (float)b1p);
+        const float an = clock.advance(a.lr, a.beta1, a.beta2);
         if (lane == 0) misc[5] = an;
       }
       __syncthreads();
@@ -1743,13 +1702,10 @@ __global__ __launch_bounds__(BORE_THREADS) void fit_bf16_mfma_kernel(const FitBf
   for (int p = tid; p < P; p += nthr) bf16_put<SHAPE>(wf, wb, bias, p, theta_g[TO::index(p)]);
 
   const long long t0 = a.at[model];
-  double b1p = pow((double)a.beta1, (double)t0);
-  double b2p = pow((double)a.beta2, (double)t0);
+  AdamClock clock(a.beta1, a.beta2, t0);
   const float omb1 = 1.f - a.beta1, omb2 = 1.f - a.beta2;
   const int steps = (N + a.B - 1) / a.B;
-  b1p *= (double)a.beta1;
-  b2p *= (double)a.beta2;
-  const float alpha_first = a.lr * sqrtf(1.f - (float)b2p) / (1.f - (float)b1p);
+  const float alpha_first = clock.advance(a.lr, a.beta1, a.beta2);
   bool first_step = true;
   __syncthreads();
 #ifdef BORE_FIT_MARKS
@@ -1839,11 +1795,7 @@ __global__ __launch_bounds__(BORE_THREADS) void fit_bf16_mfma_kernel(const FitBf
         float delta = 0.f;
         if (lane < 16 && live) {
           const float x = net.h[n][0][0];
-          const float ex = fit_exp_neg(-fabsf(x));
-          const float rden = fit_rcp(1.f + ex);
-          const float sig = x >= 0.f ? rden : ex * rden;
-          if (a.epoch_loss) eloss += fmaxf(x, 0.f) - x * zz + log1pf(ex);
-          delta = bf16_round_hw((sig - zz) * inv_nb);
+          delta = bf16_round_hw(fit_bce(x, zz, a.epoch_loss != nullptr, eloss) * inv_nb);
         }
 #pragma unroll
         for (int t = 0; t < Net::TM; ++t)
@@ -2036,9 +1988,7 @@ __global__ __launch_bounds__(BORE_THREADS) void fit_bf16_mfma_kernel(const FitBf
         BORE_WSTAMP(8);
       }
       if (wv == (BORE_THREADS / 64) - 1) {
-        b1p *= (double)a.beta1;
-        b2p *= (double)a.beta2;
-        const float an = a.lr * sqrtf(1.f - (float)b2p) / (1.f - (float)b1p);
+        const float an = clock.advance(a.lr, a.beta1, a.beta2);
         if (lane == 0) misc[5] = an;
       }
       __syncthreads();
@@ -2245,9 +2195,9 @@ __global__ __launch_bounds__(BORE_THREADS) void evaluate_kernel(const EvalArgs a
       if (lane < 16 && g * 16 + lane < a.N) {
         const float x = tile[L.aoff[n] + (wv * 16 + lane) * L.lda[n]];
         const float zz = z[g * 16 + lane];
-        lsum += fmaxf(x, 0.f) - x * zz + log1pf(expf(-fabsf(x)));
+        lsum += bce_loss(x, zz);
         const float o = L.act[n] == BORE_ACT_SIGMOID ? sigmoid_stable(x) : x;
-        csum += ((o > 0.5f) == (zz > 0.5f)) ? 1.f : 0.f;
+        csum += accuracy_hit(o, zz);
       }
       wave_lds_sync();
     }
@@ -2734,8 +2684,7 @@ extern "C" int bore_mlp_value_and_input_grad(const bore_mlp_desc *desc, int n_mo
   if (rc) return rc;
   if (a.L.w[a.L.n_layers] != 1)
     return fail(BORE_E_INVALID, "value_and_input_grad: the last Dense layer must have 1 unit");
-  if (transform < BORE_T_IDENTITY || transform > BORE_T_EXP)
-    return fail(BORE_E_INVALID, "value_and_input_grad: unknown transform %d", transform);
+  if ((rc = check_transform("value_and_input_grad", transform))) return rc;
   if (!theta || !X || !val || !grad) return fail(BORE_E_INVALID, "value_and_input_grad: null pointer");
   if (n_rows < 0) return fail(BORE_E_INVALID, "value_and_input_grad: n_rows < 0");
   if (n_rows == 0) return 0;

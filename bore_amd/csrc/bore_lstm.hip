@@ -15,8 +15,11 @@
 // Adam step in a per-model device buffer in a fixed order, and updates theta (LDS), m and v (memory)
 // once per step -- every Adam step of a call inside one launch, as the Dense fit does.
 #include "host_common.h"
+#include "mlp_math.h"
 
 namespace bore_lstm {
+
+using bore::sigmoid_stable, bore::act_grad, bore::bce_loss, bore::accuracy_hit, bore::AdamClock;
 
 constexpr int NT = 512;           // threads per workgroup (8 waves)
 constexpr int TILE = 64;          // sequences per tile (batch_size <= 64)
@@ -101,31 +104,14 @@ static int make_lay(const bore_lstm_desc *d, int T, Lay *y) {
 // --------------------------------------------------------------------------------------------------
 // device
 // --------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float sig(float x) {
-  const float e = expf(-fabsf(x));
-  const float d = 1.f + e;
-  return x >= 0.f ? 1.f / d : e / d;
-}
-
-// act(x); elu through expm1f for x <= 0, NaN in -> NaN out
+// act(x); elu through expm1f for x <= 0, NaN in -> NaN out (act_fwd's ReLU, fmaxf, gives 0 for NaN: not the same function)
 __device__ __forceinline__ float actf(int a, float x) {
   switch (a) {
     case BORE_ACT_RELU: return x > 0.f ? x : (x == x ? 0.f : x);
     case BORE_ACT_ELU: return x > 0.f ? x : expm1f(x);
-    case BORE_ACT_SIGMOID: return sig(x);
+    case BORE_ACT_SIGMOID: return sigmoid_stable(x);
     case BORE_ACT_TANH: return tanhf(x);
     default: return x;
-  }
-}
-
-// d act / d pre-activation from the activation's OUTPUT h (as oracle/bore_oracle.py writes it)
-__device__ __forceinline__ float actg(int a, float h) {
-  switch (a) {
-    case BORE_ACT_RELU: return h > 0.f ? 1.f : 0.f;
-    case BORE_ACT_ELU: return h > 0.f ? 1.f : h + 1.f;
-    case BORE_ACT_SIGMOID: return h * (1.f - h);
-    case BORE_ACT_TANH: return 1.f - h * h;
-    default: return 1.f;
   }
 }
 
@@ -225,10 +211,10 @@ __device__ void tile_forward(const Lay &a, float *sm, const Src<XT> &src, int nr
           const float *w = U + k * G1 + u;
           r0 = fmaf(hv, w[0], r0); r1 = fmaf(hv, w[H], r1); r2 = fmaf(hv, w[2 * H], r2); r3 = fmaf(hv, w[3 * H], r3);
         }
-        const float gi = sig((s0 + r0) + bias[u]);
-        const float gf = sig((s1 + r1) + bias[H + u]);
+        const float gi = sigmoid_stable((s0 + r0) + bias[u]);
+        const float gf = sigmoid_stable((s1 + r1) + bias[H + u]);
         const float gg = actf(a.act, (s2 + r2) + bias[2 * H + u]);
-        const float go = sig((s3 + r3) + bias[3 * H + u]);
+        const float go = sigmoid_stable((s3 + r3) + bias[3 * H + u]);
         const float cp = cl[b * H + u], hp = hl[b * H + u];
         const float c = gf * cp + gi * gg;
         const float h = go * actf(a.act, c);
@@ -319,10 +305,10 @@ __device__ void tile_backward(const Lay &a, float *sm, const Src<XT> &src, int n
         const float gi = g[u], gf = g[H + u], gg = g[2 * H + u], go = g[3 * H + u];
         const float c = ct[it], cp = cpv ? cpv[it] : 0.f;
         const float ac = actf(a.act, c);
-        const float dct = dcin + dh * go * actg(a.act, ac);
+        const float dct = dcin + dh * go * act_grad(a.act, ac);
         const float dzi = dct * gg * (gi * (1.f - gi));
         const float dzf = dct * cp * (gf * (1.f - gf));
-        const float dzg = dct * gi * actg(a.act, gg);
+        const float dzg = dct * gi * act_grad(a.act, gg);
         const float dzo = dh * ac * (go * (1.f - go));
         float *d = dz + b * G;
         d[u] = live ? dzi : 0.f;
@@ -392,9 +378,9 @@ __device__ float tile_bce(const Lay &a, float *sm, const float *Y, long long y_s
     const int b = it / T, t = it % T;
     const float x = logit[it], y = Y[(long long)rows[b] * y_stride + t];
     const bool live = mask[it] != 0.f;
-    const float l = fmaxf(x, 0.f) - x * y + log1pf(expf(-fabsf(x)));
+    const float l = bce_loss(x, y);
     part += live ? l : 0.f;
-    dlogit[it] = live ? (sig(x) - y) * scale : 0.f;
+    dlogit[it] = live ? (sigmoid_stable(x) - y) * scale : 0.f;
   }
   return block_sum(part, sm + a.o_red);
 }
@@ -475,8 +461,10 @@ __global__ void __launch_bounds__(NT) lstm_value_grad_kernel(VgArgs A) {
     const int b = i / T, t = i % T;
     if (t != T - 1) { dlogit[i] = 0.f; continue; }
     const float f = logit[i], s = A.negate ? -1.f : 1.f, u = s * f;
+    // objective_transform (mlp_math.h) written out: with the sign inside each arm the identity arm has no multiply,
+    // which the helper's s * dT compiles differently (same values)
     float v, dv;
-    if (A.transform == BORE_T_SIGMOID) { v = sig(u); dv = s * (v * (1.f - v)); }
+    if (A.transform == BORE_T_SIGMOID) { v = sigmoid_stable(u); dv = s * (v * (1.f - v)); }
     else if (A.transform == BORE_T_EXP) { v = expf(u); dv = s * v; }
     else { v = u; dv = s; }
     A.val[(long long)m * A.n + r0 + b] = v;
@@ -510,7 +498,7 @@ __global__ void __launch_bounds__(NT) lstm_fit_kernel(FitArgsL A) {
   float *ws = A.ws + (long long)m * a.ws_floats, *gacc = A.gacc + (long long)m * a.P;
   load_theta(a, th_g, sm);
   const long long t0 = A.at[m];
-  double b1p = pow((double)A.beta1, (double)t0), b2p = pow((double)A.beta2, (double)t0);
+  AdamClock clock(A.beta1, A.beta2, t0);
   const float omb1 = 1.f - A.beta1, omb2 = 1.f - A.beta2;
   Src<float> src;
   src.X = A.X + (long long)m * N * T * a.D;
@@ -534,9 +522,7 @@ __global__ void __launch_bounds__(NT) lstm_fit_kernel(FitArgsL A) {
       tile_backward(a, sm, src, nrows, T, ws, gacc, false);
       // Adam (ResourceApplyAdam), the l2 penalties of the loss on the weights before the update
       ++steps;
-      b1p *= (double)A.beta1;
-      b2p *= (double)A.beta2;
-      const float alpha = A.lr * sqrtf(1.f - (float)b2p) / (1.f - (float)b1p);
+      const float alpha = clock.advance(A.lr, A.beta1, A.beta2);
       float pen = 0.f;
       for (int p = threadIdx.x; p < a.P; p += NT) {
         const int li = lds_of(a, p);
@@ -599,7 +585,7 @@ __global__ void __launch_bounds__(NT) lstm_evaluate_kernel(EvalArgsL A) {
       const int b = it / T, t = it % T;
       const float y = Y[(long long)rows[b] * T + t];
       const bool live = mask[it] != 0.f;
-      h += live && ((logit[it] > 0.5f) == (y > 0.5f)) ? 1.f : 0.f;
+      h += live ? accuracy_hit(logit[it], y) : 0.f;
       n += live ? 1.f : 0.f;
     }
     const float hs = block_sum(h, sm + a.o_red), ns = block_sum(n, sm + a.o_red);
@@ -672,8 +658,7 @@ extern "C" int bore_lstm_value_and_input_grad(const bore_lstm_desc *desc, int n_
   int rc = lstm_common(desc, n_models, num_steps, &A.a, "lstm_value_and_input_grad");
   if (rc) return rc;
   if (!theta || !X || !val || !grad) return fail(BORE_E_INVALID, "lstm_value_and_input_grad: null pointer");
-  if (transform < BORE_T_IDENTITY || transform > BORE_T_EXP)
-    return fail(BORE_E_INVALID, "lstm_value_and_input_grad: unknown transform %d", transform);
+  if ((rc = check_transform("lstm_value_and_input_grad", transform))) return rc;
   if (n_rows < 0) return fail(BORE_E_INVALID, "lstm_value_and_input_grad: n_rows < 0");
   if (n_rows == 0) return 0;
   const long long tiles = (n_rows + TILE - 1) / TILE;

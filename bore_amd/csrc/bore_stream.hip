@@ -25,6 +25,7 @@
 
 #include "host_common.h"
 #include "mlp_device.h"
+#include "mlp_math.h"
 
 namespace bore {
 
@@ -250,20 +251,11 @@ __global__ __launch_bounds__(BORE_THREADS) void stream_rows_kernel(const StreamR
       if (tid < nr) out[row0 + tid] = An[tid];
     } else {
       float *Dn = ws + SROWS * (S.pre[n + 1] + S.pre[n]);
-      if (tid < nr) {  // transforms and sign as fg_rowblock (mlp_device.h)
+      if (tid < nr) {
         const float f = An[tid];
         const float u = a.sign * f;
         float T, dT;
-        if (a.transform == BORE_T_SIGMOID) {
-          T = sigmoid_stable(u);
-          dT = T * (1.f - T);
-        } else if (a.transform == BORE_T_EXP) {
-          T = expf(u);
-          dT = T;
-        } else {
-          T = u;
-          dT = 1.f;
-        }
+        objective_transform(a.transform, u, T, dT);
         out[row0 + tid] = T;
         Dn[tid] = a.sign * dT * act_grad(L.act[n], f);
       }
@@ -306,12 +298,12 @@ __global__ __launch_bounds__(BORE_THREADS) void stream_evaluate_kernel(const Str
     for (int i = tid; i < nr * D; i += nthr) A0[i] = X[row0 * D + i];
     __syncthreads();
     stream_forward<false>(S, L, th, ws, nr, true);
-    if (tid < nr) {  // loss and accuracy as evaluate_kernel defines them
+    if (tid < nr) {
       const float x = An[tid];
       const float zz = z[row0 + tid];
-      lsum += fmaxf(x, 0.f) - x * zz + log1pf(expf(-fabsf(x)));
+      lsum += bce_loss(x, zz);
       const float o = L.act[n] == BORE_ACT_SIGMOID ? sigmoid_stable(x) : x;
-      csum += ((o > 0.5f) == (zz > 0.5f)) ? 1.f : 0.f;
+      csum += accuracy_hit(o, zz);
     }
     __syncthreads();
   }
@@ -355,10 +347,8 @@ __global__ __launch_bounds__(BORE_THREADS) void stream_fit_kernel(const StreamFi
   float *A0 = ws, *An = ws + SROWS * S.pre[n];
   float *Dn = ws + SROWS * (S.pre[n + 1] + S.pre[n]);
 
-  // running beta powers in fp64, rounded to fp32 at use (fit_body)
   const long long t0 = a.at[model];
-  double b1p = pow((double)a.beta1, (double)t0);
-  double b2p = pow((double)a.beta2, (double)t0);
+  AdamClock clock(a.beta1, a.beta2, t0);
   const float omb1 = 1.f - a.beta1, omb2 = 1.f - a.beta2;
   const int steps = (N + a.B - 1) / a.B;
   float reg = L.any_l2 ? stream_penalty(S, L, th) : 0.f;  // penalty of the weights the next step's loss sees
@@ -371,9 +361,7 @@ __global__ __launch_bounds__(BORE_THREADS) void stream_fit_kernel(const StreamFi
       const int row0 = s * a.B;
       const int nb = min(a.B, N - row0);
       const float inv_nb = fit_rcp((float)nb);
-      b1p *= (double)a.beta1;
-      b2p *= (double)a.beta2;
-      const float alpha = a.lr * sqrtf(1.f - (float)b2p) / (1.f - (float)b1p);
+      const float alpha = clock.advance(a.lr, a.beta1, a.beta2);
       if (L.any_l2) ereg += reg * (float)nb;
       const int nsub = (nb + SROWS - 1) / SROWS;
       for (int sub = 0; sub < nsub; ++sub) {
@@ -388,14 +376,10 @@ __global__ __launch_bounds__(BORE_THREADS) void stream_fit_kernel(const StreamFi
         if (tid < nr) S.zt[tid] = zg[perm[r0 + tid]];
         __syncthreads();
         stream_forward<true>(S, L, th, ws, nr, true);
-        if (tid < nr) {  // BCE from logits and d loss / d logit, as fit_body
+        if (tid < nr) {  // loss and d loss / d logit
           const float x = An[tid];
           const float zz = S.zt[tid];
-          const float ex = fit_exp_neg(-fabsf(x));
-          const float rden = fit_rcp(1.f + ex);
-          const float sig = x >= 0.f ? rden : ex * rden;
-          eloss += fmaxf(x, 0.f) - x * zz + log1pf(ex);
-          Dn[tid] = (sig - zz) * inv_nb;
+          Dn[tid] = fit_bce(x, zz, true, eloss) * inv_nb;
         }
         __syncthreads();
         // ---- per layer, descending: D_{l-1} from the OLD W_l, then dW_l = A_{l-1}^T D_l and its Adam update ----
@@ -528,8 +512,7 @@ static int stream_forward_entry(const bore_mlp_desc *desc, int n_models, const f
 static int stream_value_and_input_grad(const bore_mlp_desc *desc, int n_models, const float *theta, const double *X,
                                        int64_t n_rows, int transform, int negate, float *val, double *grad,
                                        void *stream) {
-  if (transform < BORE_T_IDENTITY || transform > BORE_T_EXP)
-    return fail(BORE_E_INVALID, "value_and_input_grad: unknown transform %d", transform);
+  if (const int rc = check_transform("value_and_input_grad", transform)) return rc;
   return stream_rows(true, desc, n_models, theta, nullptr, X, n_rows, 0, transform, negate ? -1.f : 1.f, val, grad,
                      stream);
 }

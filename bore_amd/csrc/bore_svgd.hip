@@ -443,8 +443,7 @@ extern "C" int bore_svgd_optimize(const bore_mlp_desc *desc, int n_models, const
   if (n < 1 || n > BORE_SVGD_MAX_PARTICLES)  // (what fits is decided by the LDS check below: 32 n D bytes of state)
     return fail(BORE_E_UNSUPPORTED, "svgd_optimize: 1..%d particles per launch", BORE_SVGD_MAX_PARTICLES);
   const bool big = n > BORE_BATCH_MAX;  // (no kernel matrix in LDS: svgd_big_kernel)
-  if (transform < BORE_T_IDENTITY || transform > BORE_T_EXP)
-    return fail(BORE_E_INVALID, "svgd_optimize: unknown transform %d", transform);
+  if (const int rc = check_transform("svgd_optimize", transform)) return rc;
   if (opts->n_iter < 0 || (opts->distortion != 0 && opts->distortion != 1))
     return fail(BORE_E_INVALID, "svgd_optimize: bad options");
   if ((lb == nullptr) != (ub == nullptr)) return fail(BORE_E_INVALID, "svgd_optimize: lb and ub go together");

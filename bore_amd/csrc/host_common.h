@@ -22,6 +22,13 @@ inline int fail(int code, const char *fmt, ...) {
   return code;
 }
 
+// The objective transform every value-and-gradient entry point takes (BORE_T_*).
+inline int check_transform(const char *who, int transform) {
+  if (transform < BORE_T_IDENTITY || transform > BORE_T_EXP)
+    return fail(BORE_E_INVALID, "%s: unknown transform %d", who, transform);
+  return 0;
+}
+
 #define HIP_TRY(expr)                                                                      \
   do {                                                                                     \
     hipError_t e_ = (expr);                                                                \

@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include "mlp_layout.h"
+#include "mlp_math.h"
 #include "mlp_shapes.h"
 
 // A phase body that the fused iteration kernel runs inside its resident loop derives its per-lane
@@ -28,66 +29,6 @@
 namespace bore {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float sigmoid_stable(float x) {
-  float e = expf(-fabsf(x));  // expf: ocml, <=1 ulp
-  float d = 1.f + e;
-  return x >= 0.f ? 1.f / d : e / d;
-}
-
-// ---- the FIT's arithmetic: "<= 1 ulp per operation" (DESIGN.md 2), hardware rcp / sqrt / 2^t ----
-__device__ __forceinline__ float fit_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
-__device__ __forceinline__ float fit_sqrt(float x) { return __builtin_amdgcn_sqrtf(x); }
-// exp(x) for x <= 0: 2^(x log2 e) with the product's rounding error fed back (the argument's error
-// would otherwise be |x| 2^-24 in the exponent); flushes to zero below 2^-126 like the result's use
-// (1 + e) does not notice
-__device__ __forceinline__ float fit_exp_neg(float x) {
-  const float L2E = 1.442695040888963f, L2E_LO = 1.925963033500e-8f;  // log2(e) = hi + lo
-  const float t = x * L2E;
-  const float r = fmaf(x, L2E_LO, fmaf(x, L2E, -t));                 // exact remainder of the product
-  const float e = __builtin_amdgcn_exp2f(t);
-  return fmaf(e, r * 0.6931471805599453f, e);                          // 2^(t + r) = 2^t (1 + r ln 2)
-}
-// elu(x) in the fit (round 6).  The reference's layers are Keras `activation="elu"` (plugins/hpbandster/base.py:
-// 152-155), whose TF kernel forms exp(x) - 1 for x < 0 (Eigen: features.exp() - 1).  ocml's expm1f is ~60
-// instructions with branches, 24 calls per lane in a forward pass of 16->32-32-32-1: 6.7 k of an 18 k-cycle Adam
-// step (profiles/r6/fit_marks_plugin.txt).  Here, for x < 0: the hardware's 2^(x log2 e) minus one -- the error of
-// the rounded exponent is e^x |x| 2^-24 <= 0.37 x 2^-24 in absolute terms, under the half-ulp the exponential itself
-// may be off near 1, so no feedback term; the subtraction is exact from x >= -0.69 on -- and the series
-// x + x^2/2 + x^3/6 + x^4/24 where that difference would cancel (|x| < 1/32: truncation x^5 / 120 < 2^-26 |x|).
-// Absolute error <= 2^-24 everywhere against the float64 oracle's expm1, relative <= 2e-6 (at the seam).
-__device__ __forceinline__ float fit_elu(float x) {
-  const float xn = fminf(x, 0.f);
-  const float big = __builtin_amdgcn_exp2f(xn * 1.442695040888963f) - 1.f;
-  const float ser = xn * fmaf(xn, fmaf(xn, fmaf(xn, 1.f / 24.f, 1.f / 6.f), 0.5f), 1.f);
-  const float neg = xn > -0.03125f ? ser : big;
-  return x > 0.f ? x : neg;
-}
-
-// FIT: the caller is a fit kernel (fit_elu instead of ocml's expm1f; everything else alike)
-template <bool FIT = false>
-__device__ __forceinline__ float act_fwd(int a, float x) {
-  switch (a) {
-    case BORE_ACT_RELU: return fmaxf(x, 0.f);
-    case BORE_ACT_ELU:
-      if constexpr (FIT) return fit_elu(x);
-      else return x > 0.f ? x : expm1f(x);
-    case BORE_ACT_SIGMOID: return sigmoid_stable(x);
-    case BORE_ACT_TANH: return tanhf(x);
-    default: return x;
-  }
-}
-
-// d act / d pre-activation, from the activation OUTPUT h.
-__device__ __forceinline__ float act_grad(int a, float h) {
-  switch (a) {
-    case BORE_ACT_RELU: return h > 0.f ? 1.f : 0.f;
-    case BORE_ACT_ELU: return h > 0.f ? 1.f : h + 1.f;
-    case BORE_ACT_SIGMOID: return h * (1.f - h);
-    case BORE_ACT_TANH: return 1.f - h * h;
-    default: return 1.f;
-  }
-}
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -359,16 +300,7 @@ __device__ __forceinline__ void fg_rowblock(const MlpLayout &L, int n, const flo
     const float f = tile[L.aoff[n] + row * L.lda[n]];
     const float u = sign * f;
     float T, dT;
-    if (transform == BORE_T_SIGMOID) {
-      T = sigmoid_stable(u);
-      dT = T * (1.f - T);
-    } else if (transform == BORE_T_EXP) {
-      T = expf(u);
-      dT = T;
-    } else {
-      T = u;
-      dT = 1.f;
-    }
+    objective_transform(transform, u, T, dT);
     val_out[row] = T;
     tile[L.doff[n] + row * L.lda[n]] = sign * dT * act_grad(L.act[n], f);
   }

@@ -392,16 +392,7 @@ struct RegNet {
     const float f = h[n][0][0];
     const float u = sign * f;
     float Tv, dT;
-    if (transform == BORE_T_SIGMOID) {
-      Tv = sigmoid_stable(u);
-      dT = Tv * (1.f - Tv);
-    } else if (transform == BORE_T_EXP) {
-      Tv = expf(u);
-      dT = Tv;
-    } else {
-      Tv = u;
-      dT = 1.f;
-    }
+    objective_transform(transform, u, Tv, dT);
     set_output_delta(sign * dT * act_grad(act_of<n>(), f));
     backward<n, 1>(th);
     return Tv;

@@ -1,11 +1,13 @@
-"""A/B of two builds of libbore_hip.so on the wide fits: bit-identity of the results and time per
-Adam step (GPU box).  usage: python tools/ab_fit.py  (runs itself once per library)"""
+"""A/B of two builds of libbore_hip.so on the fits: bit-identity of the results and time per Adam step, median
+(min .. max) of REPS timed calls (GPU box).  usage: python tools/ab_fit.py [other]  (runs itself once per library:
+the shipped one and bore_amd/csrc/libbore_hip_<other>.so, default prev)"""
 import os, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 CASES = [("shape3_f32", 16, [64, 64, 64, 1], "float32"), ("shape3_bf16", 16, [64, 64, 64, 1], "bfloat16"),
          ("shape4_bf16", 32, [128, 128, 1], "bfloat16"), ("shape2_f32", 6, [32, 32, 1], "float32"),
-         ("shape1_f32", 2, [16, 16, 1], "float32")]
+         ("shape1_f32", 2, [16, 16, 1], "float32"), ("stream_f32", 8, [256, 256, 1], "float32")]  # (the streamed flavour)
+REPS = 7
 
 
 def child(tag):
@@ -24,26 +26,29 @@ def child(tag):
         X = torch.from_numpy(rs.uniform(size=(L, N, D)).astype(np.float32)).cuda()
         z = torch.from_numpy((rs.uniform(size=(L, N)) < 0.25).astype(np.float32)).cuda()
         ops.mlp_fit(desc, th, m, v, t, X, z, E, 64, seed=3, want_loss=False)   # also the warm-up
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        ops.mlp_fit(desc, th, m, v, t, X, z, E, 64, seed=3, epoch0=E, want_loss=False)
-        torch.cuda.synchronize()
-        dt = time.perf_counter() - t0
-        steps = E * -(-N // 64)
-        print(f"{tag} {name}: {1e6 * dt / steps:7.2f} us per Adam step ({L} models, N={N})", flush=True)
+        steps, us = E * -(-N // 64), []
+        for r in range(1, REPS + 1):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            ops.mlp_fit(desc, th, m, v, t, X, z, E, 64, seed=3, epoch0=r * E, want_loss=False)
+            torch.cuda.synchronize()
+            us.append(1e6 * (time.perf_counter() - t0) / steps)
+        print(f"{tag} {name}: {np.median(us):7.2f} ({min(us):.2f} .. {max(us):.2f}) us per Adam step "
+              f"({L} models, N={N}, {REPS} calls)", flush=True)
         out[name + "_th"], out[name + "_m"], out[name + "_v"] = (a.cpu().numpy() for a in (th, m, v))
     np.savez(os.path.join(ROOT, "gpurun_out", f"ab_{tag}.npz"), **out)
 
 
 if __name__ == "__main__":
-    if len(sys.argv) > 1:
-        child(sys.argv[1])
+    if len(sys.argv) > 2:
+        child(sys.argv[2])
         sys.exit(0)
     import numpy as np
+    other = sys.argv[1] if len(sys.argv) > 1 else "prev"
     libs = {"new": os.path.join(ROOT, "bore_amd", "csrc", "libbore_hip.so"),
-            "prev": os.path.join(ROOT, "bore_amd", "csrc", "libbore_hip_prev.so")}
-    for tag, path in libs.items():
-        subprocess.run([sys.executable, __file__, tag], env=dict(os.environ, BORE_LIB_PATH=path), check=True)
+            "prev": os.path.join(ROOT, "bore_amd", "csrc", f"libbore_hip_{other}.so")}
+    for tag, path in 2 * list(libs.items()):  # (twice, alternating: drift hits both builds alike)
+        subprocess.run([sys.executable, __file__, "--child", tag], env=dict(os.environ, BORE_LIB_PATH=path), check=True)
     a, b = (np.load(os.path.join(ROOT, "gpurun_out", f"ab_{t}.npz")) for t in ("new", "prev"))
     for k in a.files:
         same = np.array_equal(a[k], b[k])
