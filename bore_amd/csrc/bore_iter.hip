@@ -377,11 +377,7 @@ __global__ __launch_bounds__(BORE_THREADS, OCC) void queue_kernel(const IterArgs
   }
 }
 
-// One fused launch for the batch currently set (bore_set_batch): fills *h (pinned host copy of the
-// arguments, at the head of a staging block of upload_bytes that also holds x_new / y_new / ids /
-// its), uploads the block to d_args and launches.
-// Returns BORE_E_UNSUPPORTED when the model is not static shape 1: the caller falls back to the
-// launch chain.
+// ---- host side ------------------------------------------------------------------------------------
 // The static shape whose fused kernels run the model, or 0 (the caller keeps the launch chain).  Shape 5 only at its
 // 16 compiled inputs: with fewer the fit runs zero-padded through a repacked copy (fit_padded), which the fused
 // kernel has no phase for.
@@ -392,7 +388,6 @@ static int iteration_shape(const bore_mlp_desc *desc) {
   if (f == 5 && desc->input_dim == 16 && bore_flavour_on(5)) return 5;
   return 0;
 }
-static int iteration_supported(const bore_mlp_desc *desc) { return iteration_shape(desc) != 0; }
 
 // Which of FusedFlavours a build holds: shape 1's fused kernels are in every build (BORE_SHAPE_MASK has never covered
 // them: an experiment build's engine runs 2->16-16-1 whatever else it leaves out), shape 5's follow the mask.
@@ -434,37 +429,81 @@ static int iteration_loops_per_cu(int shape, size_t lds_bytes, int *per_cu_out) 
   return 0;
 }
 
-static int iteration_launch(const bore_mlp_desc *desc, int n_slots, float *theta, float *adam_m,
-                            float *adam_v, int64_t *adam_t, double *X_seen, double *y_seen,
-                            float *X32, float *z, const double *x_new, const double *y_new,
-                            double gamma, int epochs, int batch_size, uint64_t seed,
-                            int64_t loop_id0, const bore_adam_cfg *adam, int64_t num_samples,
-                            const double *low, const double *high, int num_starts, int transform,
-                            const bore_lbfgsb_opts *opts, double *x0, int32_t *idx, double *x,
-                            double *fun, double *jac, int32_t *info, IterArgs *h,
-                            const IterArgs *d_args, size_t upload_bytes, void *stream,
-                            int queue_wgs = 0, const QueueEntry *q_ring = nullptr,
-                            unsigned long long *q_head = nullptr, int q_mask = 0, int *per_cu_out = nullptr,
-                            const unsigned long long *q_tail_host = nullptr) {
+// What is the same for every fused launch of an engine: bore_engine.hip's async_create fills it once, and its
+// async_alloc moves the four record pointers when the records are reallocated.
+struct IterEngine {
+  const bore_mlp_desc *desc;
+  float *theta, *adam_m, *adam_v;
+  int64_t *adam_t;
+  double *X_seen, *y_seen;  // records: device [L][cap][D], [L][cap]
+  float *X32, *z;           // device [L][cap][D], [L][cap]
+  double gamma;             // the fit: labels' quantile, epochs, batch, shuffle stream, Adam
+  int epochs, batch_size;
+  uint64_t seed;
+  int64_t loop_id0;
+  const bore_adam_cfg *adam;
+  int64_t num_samples;      // the argmax: screened samples, box, restarts and their L-BFGS-B
+  const double *low, *high;
+  int num_starts, transform;
+  const bore_lbfgsb_opts *opts;
+  int n_loops;  // L: the slots a worker's staging block is laid out for
+};
+
+// A WORKER of the asynchronous engine (bore_engine.hip) is a stream that runs one launch -- the fused kernel, or the
+// chain append, labels, fit, sample + screen, restarts + pick -- over whatever loops are ready when it becomes free.
+struct Worker {
+  hipStream_t stream = nullptr;
+  hipEvent_t done = nullptr, ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  bool busy = false;
+  // staging: ids [L] | its [L] (int32) then x_new [L][D] | y_new [L] (fp64), host and device
+  int32_t *h_int = nullptr, *d_int = nullptr;
+  double *h_dbl = nullptr, *d_dbl = nullptr;
+  // per-slot outputs of the launch (device)
+  double *x0 = nullptr, *x = nullptr, *jac = nullptr, *fun = nullptr;
+  int32_t *idx = nullptr, *info = nullptr;
+  IterArgs *h_args = nullptr, *d_args = nullptr;  // fused iteration kernel: pinned / device copy
+  size_t stage_bytes = 0;                          // (start of the worker's staging block)
+};
+
+// The work queue a queue_kernel launch is fed through (IterArgs::q_*), and the workgroups of that launch.
+struct IterQueue {
+  const QueueEntry *ring;
+  unsigned long long *head;
+  int mask;
+  const unsigned long long *tail_host;
+  int wgs;
+};
+
+struct IterPlan {
+  int shape;
+  size_t lds_bytes;      // dynamic LDS per loop: the largest of the phases'
+  size_t part_bytes[4];  // fit, screen, restarts, labels (BORE_ASYNC_DEBUG's line)
+};
+
+// What a fused launch of `n_slots` loops of the batch currently set (bore_set_batch) on worker w needs: fills the
+// arguments *h, says which static shape runs the model and how much LDS a loop takes, and raises the fused kernels'
+// LDS limits to that.  Asked on its own by the engine's choice of schedule; both launches below start from it.
+// BORE_E_UNSUPPORTED when the model is neither static shape 1 nor 5 at 16 inputs: the caller keeps the launch chain.
+static int iteration_plan(const IterEngine &E, const Worker &w, int n_slots, IterArgs *h, IterPlan *plan) {
   if (!g_batch) return fail(BORE_E_INVALID, "iteration_launch: no batch set");
   const int64_t cap = g_batch->cap;
   size_t lf = 0, ls = 0, lb = 0;
   int sf = 0, ss = 0, sb = 0, blocks = 0;
-  int rc = fit_build(desc, n_slots, theta, adam_m, adam_v, adam_t, X32, z, cap, epochs, batch_size,
-                     nullptr, seed, loop_id0, 0, adam, nullptr, h->f, lf, sf);
+  int rc = fit_build(E.desc, n_slots, E.theta, E.adam_m, E.adam_v, E.adam_t, E.X32, E.z, cap, E.epochs, E.batch_size,
+                     nullptr, E.seed, E.loop_id0, 0, E.adam, nullptr, h->f, lf, sf);
   if (rc) return rc < 0 ? rc : fail(BORE_E_INVALID, "iteration_launch: epochs must be positive");
-  const SampleSpec spec{seed, loop_id0, 0, low, high};
-  if ((rc = screen_build(desc, n_slots, theta, nullptr, &spec, num_samples, 0, num_starts, x0, idx,
+  const SampleSpec spec{E.seed, E.loop_id0, 0, E.low, E.high};
+  if ((rc = screen_build(E.desc, n_slots, E.theta, nullptr, &spec, E.num_samples, 0, E.num_starts, w.x0, w.idx,
                          nullptr, h->s, ls, ss)))
     return rc;
-  if ((rc = lbfgsb_build(desc, n_slots, theta, transform, 1, x0, num_starts, low, high, opts, x, fun,
-                         jac, info, h->b, lb, sb, blocks)))
+  if ((rc = lbfgsb_build(E.desc, n_slots, E.theta, E.transform, 1, w.x0, E.num_starts, E.low, E.high, E.opts, w.x,
+                         w.fun, w.jac, w.info, h->b, lb, sb, blocks)))
     return rc;
-  const int shape = iteration_shape(desc);
+  const int shape = iteration_shape(E.desc);
   if (!shape || sf != shape || ss != shape || sb != shape || blocks != 1)
     return fail(BORE_E_UNSUPPORTED, "iteration_launch: static shape 1, or 5 at 16 inputs, one workgroup per loop");
-  h->X_seen = X_seen; h->y_seen = y_seen; h->X32 = X32; h->z = z;
-  h->x_new = x_new; h->y_new = y_new;
+  h->X_seen = E.X_seen; h->y_seen = E.y_seen; h->X32 = E.X32; h->z = E.z;
+  h->x_new = w.d_dbl; h->y_new = w.d_dbl + (size_t)E.n_loops * E.desc->input_dim;
   h->stamps = reinterpret_cast<long long *>(g_batch->stamps);
   h->b.stamps = h->stamps;
   h->targets = g_batch->targets;
@@ -474,16 +513,17 @@ static int iteration_launch(const bore_mlp_desc *desc, int n_slots, float *theta
                         g_batch->abort_flag;
   if (!resident) h->targets = nullptr;  // one iteration per launch
   h->wait_ticks = resident ? g_batch->wait_ticks : 0;
-  h->gamma = gamma;
-  h->D = desc->input_dim;
+  h->gamma = E.gamma;
+  h->D = E.desc->input_dim;
   h->progress = 0;
-  h->q_ring = q_ring; h->q_head = q_head; h->q_mask = q_mask; h->q_tail_host = q_tail_host;
+  h->q_ring = nullptr; h->q_head = nullptr; h->q_mask = 0; h->q_tail_host = nullptr;
   size_t floats = lf > ls ? lf : ls;
   floats = floats > lb ? floats : lb;
   const size_t labels_floats = 2 * ((size_t)cap + 2);
   floats = floats > labels_floats ? floats : labels_floats;
-  // (every kernel the shape may be launched with below, up front)
-  rc = bore_with_flavour<fused_flavour_on>(FusedFlavours{}, shape, [&](auto S) {
+  *plan = IterPlan{shape, floats * 4, {lf * 4, ls * 4, lb * 4, labels_floats * 4}};
+  // (every kernel the shape may be launched with, up front)
+  return bore_with_flavour<fused_flavour_on>(FusedFlavours{}, shape, [&](auto S) {
     int rc = 0;
     if ((rc = allow_lds(iteration_kernel<S(), true, 2>, floats * 4)) || (rc = allow_lds(iteration_kernel<S(), false, 2>, floats * 4)) ||
         (rc = allow_lds(queue_kernel<S(), 2>, floats * 4)))
@@ -492,44 +532,56 @@ static int iteration_launch(const bore_mlp_desc *desc, int n_slots, float *theta
       if ((rc = allow_lds(iteration_kernel<S(), true, 3>, floats * 4)) || (rc = allow_lds(queue_kernel<S(), 3>, floats * 4))) return rc;
     return 0;
   });
-  if (rc) return rc;
-  auto launch = [&](auto kernel, int workgroups) {
-    hipLaunchKernelGGL(kernel, dim3(workgroups), dim3(BORE_THREADS), floats * 4, (hipStream_t)stream, d_args);
-    HIP_TRY(hipGetLastError());
-    return 0;
-  };
-  if (per_cu_out) {  // (a question, not a launch: how many loops of this model one CU holds)
-    *per_cu_out = 0;
-    return iteration_loops_per_cu(shape, floats * 4, per_cu_out);
-  }
-  if (queue_wgs > 0) {  // the work-queue form: a fixed grid, fed by the host through q_ring
-    if (!q_ring || !q_head || !q_tail_host || !g_batch->ynew || !g_batch->abort_flag)
-      return fail(BORE_E_INVALID, "iteration_launch: incomplete work queue");
-    h->targets = nullptr;
-    h->wait_ticks = 0;
-    HIP_TRY(hipMemcpyAsync(const_cast<IterArgs *>(d_args), h, sizeof(IterArgs), hipMemcpyHostToDevice,
-                           (hipStream_t)stream));
-    return bore_with_flavour<fused_flavour_on>(FusedFlavours{}, shape, [&](auto S) {
-      // (no more workgroups than two per CU: the kernel with the whole register file)
-      if constexpr (fused_most_per_cu(S()) == 3)
-        if (queue_wgs > 2 * device_cus()) return launch(queue_kernel<S(), 3>, queue_wgs);
-      return launch(queue_kernel<S(), 2>, queue_wgs);
-    });
-  }
+}
+
+template <typename K>
+static int fused_launch(K kernel, int workgroups, const IterPlan &p, const Worker &w) {
+  hipLaunchKernelGGL(kernel, dim3(workgroups), dim3(BORE_THREADS), p.lds_bytes, w.stream, (const IterArgs *)w.d_args);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// The work-queue launch on worker w: a fixed grid of q.wgs workgroups, fed by the host through q.ring.  Only the
+// arguments are uploaded (ids[] is the identity, the rows come through ynew).
+static int iteration_launch_queue(const IterEngine &E, Worker &w, int n_slots, const IterQueue &q) {
+  IterArgs *h = w.h_args;
+  IterPlan p;
+  if (const int rc = iteration_plan(E, w, n_slots, h, &p)) return rc;
+  if (q.wgs < 1 || !q.ring || !q.head || !q.tail_host || !g_batch->ynew || !g_batch->abort_flag)
+    return fail(BORE_E_INVALID, "iteration_launch: incomplete work queue");
+  h->q_ring = q.ring; h->q_head = q.head; h->q_mask = q.mask; h->q_tail_host = q.tail_host;
+  h->targets = nullptr;
+  h->wait_ticks = 0;
+  HIP_TRY(hipMemcpyAsync(w.d_args, h, sizeof(IterArgs), hipMemcpyHostToDevice, w.stream));
+  return bore_with_flavour<fused_flavour_on>(FusedFlavours{}, p.shape, [&](auto S) {
+    // (no more workgroups than two per CU: the kernel with the whole register file)
+    if constexpr (fused_most_per_cu(S()) == 3)
+      if (q.wgs > 2 * device_cus()) return fused_launch(queue_kernel<S(), 3>, q.wgs, p, w);
+    return fused_launch(queue_kernel<S(), 2>, q.wgs, p, w);
+  });
+}
+
+// One fused launch on worker w for the `n_slots` loops of the batch currently set: one upload of the worker's staging
+// block (w.h_args heads it: arguments | per-slot inputs | index lists), a workgroup per slot -- resident ones, which
+// go on to later iterations of their loops, when the batch asks for that and the device holds them all.
+static int iteration_launch(const IterEngine &E, Worker &w, int n_slots) {
+  IterArgs *h = w.h_args;
+  IterPlan p;
+  int rc;
+  if ((rc = iteration_plan(E, w, n_slots, h, &p))) return rc;
   if (h->wait_ticks > 0) {  // waiting workgroups hold their slots: only when all of them fit at once
     int per_cu = 0;
-    if ((rc = iteration_loops_per_cu(shape, floats * 4, &per_cu))) return rc;
+    if ((rc = iteration_loops_per_cu(p.shape, p.lds_bytes, &per_cu))) return rc;
     if (getenv("BORE_ASYNC_DEBUG"))
-      fprintf(stderr, "[bore] fused kernel: %zu B of LDS per loop (fit %zu, screen %zu, restarts %zu, labels %zu), %d loops per CU\n", floats * 4, lf * 4, ls * 4, lb * 4, labels_floats * 4, per_cu);
+      fprintf(stderr, "[bore] fused kernel: %zu B of LDS per loop (fit %zu, screen %zu, restarts %zu, labels %zu), %d loops per CU\n",
+              p.lds_bytes, p.part_bytes[0], p.part_bytes[1], p.part_bytes[2], p.part_bytes[3], per_cu);
     if (g_batch->resident_loops > per_cu * device_cus()) h->wait_ticks = 0;
   }
-  // h heads the caller's staging block (arguments | per-slot inputs | index lists): one upload
-  HIP_TRY(hipMemcpyAsync(const_cast<IterArgs *>(d_args), h, upload_bytes, hipMemcpyHostToDevice,
-                         (hipStream_t)stream));
-  return bore_with_flavour<fused_flavour_on>(FusedFlavours{}, shape, [&](auto S) {
+  HIP_TRY(hipMemcpyAsync(w.d_args, h, w.stage_bytes, hipMemcpyHostToDevice, w.stream));
+  return bore_with_flavour<fused_flavour_on>(FusedFlavours{}, p.shape, [&](auto S) {
     if constexpr (fused_most_per_cu(S()) == 3)  // (three loops per CU: see iteration_kernel)
-      if (h->wait_ticks > 0 && g_batch->resident_loops > 2 * device_cus()) return launch(iteration_kernel<S(), true, 3>, n_slots);
-    if (h->wait_ticks > 0) return launch(iteration_kernel<S(), true, 2>, n_slots);
-    return launch(iteration_kernel<S(), false, 2>, n_slots);
+      if (h->wait_ticks > 0 && g_batch->resident_loops > 2 * device_cus()) return fused_launch(iteration_kernel<S(), true, 3>, n_slots, p, w);
+    if (h->wait_ticks > 0) return fused_launch(iteration_kernel<S(), true, 2>, n_slots, p, w);
+    return fused_launch(iteration_kernel<S(), false, 2>, n_slots, p, w);
   });
 }
