@@ -29,6 +29,7 @@ os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 MAX_LAYERS = 8
 BATCH_MAX = 64
 STREAM_MAX_UNITS = 512   # include/bore_hip.h BORE_STREAM_MAX_UNITS
+STREAM_MAX_SAMPLES = 16384   # include/bore_hip.h BORE_STREAM_MAX_SAMPLES
 
 ACT = dict(linear=0, relu=1, elu=2, sigmoid=3, tanh=4)
 TRANSFORM = dict(identity=0, sigmoid=1, exp=2)
@@ -43,6 +44,7 @@ EXPORTS = [
     "bore_engine_state", "bore_engine_get_stats", "bore_engine_destroy", "bore_objective_branin01",
     "bore_lstm_param_count", "bore_lstm_forward", "bore_lstm_value_and_input_grad", "bore_lstm_fit",
     "bore_lstm_evaluate", "bore_mlp_streamed",
+    "bore_stream_screen_topk", "bore_stream_sample_screen_topk", "bore_stream_lbfgsb_minimize",
 ]
 
 
@@ -244,6 +246,9 @@ def lib():
                                 C.POINTER(AdamCfg), vp, vp]
     L.bore_lstm_evaluate.argtypes = [lp, i32, vp, vp, vp, i64, i32, f32, vp, vp, vp]
     L.bore_mlp_streamed.argtypes = [dp]
+    L.bore_stream_screen_topk.argtypes = L.bore_screen_topk.argtypes
+    L.bore_stream_sample_screen_topk.argtypes = L.bore_sample_screen_topk.argtypes
+    L.bore_stream_lbfgsb_minimize.argtypes = L.bore_lbfgsb_minimize.argtypes
     for name in EXPORTS:
         if name not in ("bore_last_error", "bore_param_count", "bore_lstm_param_count", "bore_engine_size",
                         "bore_engine_destroy", "bore_set_batch"):

@@ -184,6 +184,73 @@ __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v)
   return v;
 }
 
+// The selection stage of the screen, shared by screen_body and the streamed flavour's selection kernel
+// (bore_stream.hip): sort keys from predictions, the R best rows, their gather in fp64.
+//   keys  LDS, [n_pad + 32] (n_pad: the power of two >= Ns; behind it 4 wave minima, the pick, R <= 16 picks)
+// ascending key == descending prediction, ties to the lower row.  Called by the whole workgroup (tid of nthr).
+__device__ __forceinline__ void screen_keys_from_pred(const int tid, const int nthr, unsigned long long *keys,
+                                                      const float *pred, const int Ns) {
+  for (int r = tid; r < Ns; r += nthr) keys[r] = ((unsigned long long)(~orderable(pred[r])) << 32) | (unsigned)r;
+}
+
+template <typename XVal>
+__device__ __forceinline__ void screen_select(const int tid, const int nthr, unsigned long long *keys, const int Ns,
+                                              const int n_pad, const int R, const int D, int *idx_out, double *x0,
+                                              XVal xval) {
+  for (int i = Ns + tid; i < n_pad; i += nthr) keys[i] = ~0ULL;
+  __syncthreads();
+
+  if (R <= 16) {
+    // R passes of "smallest key greater than the previous pick" (keys are distinct)
+    unsigned long long *red = keys + n_pad;  // [4] wave minima + [1] the pick; picks at [8..8+R)
+    unsigned long long prev = 0;
+    for (int r = 0; r < R; ++r) {
+      unsigned long long best = ~0ULL;
+      for (int i = tid; i < Ns; i += nthr) {
+        const unsigned long long k = keys[i];
+        if ((r == 0 || k > prev) && k < best) best = k;
+      }
+      best = wave_min_u64(best);
+      if ((tid & 63) == 0) red[tid >> 6] = best;
+      __syncthreads();
+      if (tid == 0) {
+        unsigned long long b = red[0];
+        for (int w = 1; w < (nthr >> 6); ++w) b = red[w] < b ? red[w] : b;
+        red[4] = b;
+        red[8 + r] = b;
+        idx_out[r] = (int)(unsigned)(b & 0xFFFFFFFFu);
+      }
+      __syncthreads();
+      prev = red[4];
+    }
+  } else {
+    // bitonic sort of the padded key array
+    for (int k = 2; k <= n_pad; k <<= 1)
+      for (int j = k >> 1; j > 0; j >>= 1) {
+        for (int i = tid; i < n_pad; i += nthr) {
+          const int ixj = i ^ j;
+          if (ixj > i) {
+            const unsigned long long x = keys[i], y = keys[ixj];
+            const bool up = (i & k) == 0;
+            if ((x > y) == up) {
+              keys[i] = y;
+              keys[ixj] = x;
+            }
+          }
+        }
+        __syncthreads();
+      }
+    for (int r = tid; r < R; r += nthr) idx_out[r] = (int)(unsigned)(keys[r] & 0xFFFFFFFFu);
+  }
+  __syncthreads();
+  // gather the chosen rows; the picks are still in LDS
+  const unsigned long long *picks = R <= 16 ? keys + n_pad + 8 : keys;
+  for (int i = tid; i < R * D; i += nthr) {
+    const int r = i / D, d = i - r * D;
+    x0[i] = xval((long long)(unsigned)(picks[r] & 0xFFFFFFFFu), d);
+  }
+}
+
 // MODE 0: the whole screen in one workgroup per model.  For ONE (or a few) wide models that leaves
 // the device idle while a single CU walks thousands of candidates, so the launcher may split it:
 // MODE 1 = the predictions only, grid (models, parts), workgroup `part` taking every parts-th
@@ -280,63 +347,8 @@ __device__ __forceinline__ void screen_body(const ScreenArgs &a, const long long
       }
     }
   if constexpr (MODE == 1) return;
-  if constexpr (MODE == 2)
-    for (int r = tid; r < Ns; r += nthr)
-      keys[r] = ((unsigned long long)(~orderable(a.pred[model * a.n_samples + r])) << 32) | (unsigned)r;
-  for (int i = Ns + tid; i < a.n_pad; i += nthr) keys[i] = ~0ULL;
-  __syncthreads();
-
-  int *idx_out = a.idx + model * a.R;
-  if (a.R <= 16) {
-    // R passes of "smallest key greater than the previous pick" (keys are distinct)
-    unsigned long long *red = keys + a.n_pad;  // [4] wave minima + [1] the pick; picks at [8..8+R)
-    unsigned long long prev = 0;
-    for (int r = 0; r < a.R; ++r) {
-      unsigned long long best = ~0ULL;
-      for (int i = tid; i < Ns; i += nthr) {
-        const unsigned long long k = keys[i];
-        if ((r == 0 || k > prev) && k < best) best = k;
-      }
-      best = wave_min_u64(best);
-      if ((tid & 63) == 0) red[tid >> 6] = best;
-      __syncthreads();
-      if (tid == 0) {
-        unsigned long long b = red[0];
-        for (int w = 1; w < (nthr >> 6); ++w) b = red[w] < b ? red[w] : b;
-        red[4] = b;
-        red[8 + r] = b;
-        idx_out[r] = (int)(unsigned)(b & 0xFFFFFFFFu);
-      }
-      __syncthreads();
-      prev = red[4];
-    }
-  } else {
-    // bitonic sort of the padded key array
-    for (int k = 2; k <= a.n_pad; k <<= 1)
-      for (int j = k >> 1; j > 0; j >>= 1) {
-        for (int i = tid; i < a.n_pad; i += nthr) {
-          const int ixj = i ^ j;
-          if (ixj > i) {
-            const unsigned long long x = keys[i], y = keys[ixj];
-            const bool up = (i & k) == 0;
-            if ((x > y) == up) {
-              keys[i] = y;
-              keys[ixj] = x;
-            }
-          }
-        }
-        __syncthreads();
-      }
-    for (int r = tid; r < a.R; r += nthr) idx_out[r] = (int)(unsigned)(keys[r] & 0xFFFFFFFFu);
-  }
-  __syncthreads();
-  // gather the chosen rows; the picks are still in LDS
-  const unsigned long long *picks = a.R <= 16 ? keys + a.n_pad + 8 : keys;
-  double *x0 = a.x0 + model * (long long)a.R * D;
-  for (int i = tid; i < a.R * D; i += nthr) {
-    const int r = i / D, d = i - r * D;
-    x0[i] = xval((long long)(unsigned)(picks[r] & 0xFFFFFFFFu), d);
-  }
+  if constexpr (MODE == 2) screen_keys_from_pred(tid, nthr, keys, a.pred + model * a.n_samples, Ns);
+  screen_select(tid, nthr, keys, Ns, a.n_pad, a.R, D, a.idx + model * a.R, a.x0 + model * (long long)a.R * D, xval);
 }
 
 template <int SHAPE, bool BF16 = false, int MODE = 0>
@@ -1121,11 +1133,13 @@ __global__ __launch_bounds__(3 * BORE_THREADS) void lbfgsb_kernel_w12(const Lbfg
 // two triangles of one block, lbfgsb.h: 90 registers spilled, 8.45 ms per million evaluation requests of config 2
 // against 7.93 for twelve waves on the same inputs, profiles/r6/ab_log.txt.  Not kept.)
 
-static int lbfgsb_build(const bore_mlp_desc *desc, int n_models, const float *theta,
-                        int transform, int negate, const double *x0, int num_starts,
-                        const double *lb, const double *ub, const bore_lbfgsb_opts *opts, double *x,
-                        double *fun, double *jac, int32_t *info, LbfgsbArgs &a, size_t &lds_floats,
-                        int &flavour_out, int &blocks_out, int *waves_out = nullptr) {
+// The argument checks of the restart entry points and what they convert: the box (nbd: 0 unbounded, 1 lower, 2 both,
+// 3 upper, as lbfgsb.h takes it) and SciPy's options as the optimiser's.  One definition for bore_lbfgsb_minimize and
+// the streamed flavour's bore_stream_lbfgsb_minimize (bore_stream.hip).  No HIP call.
+static int lbfgsb_check_args(const bore_mlp_desc *desc, int n_models, const float *theta, int transform,
+                             const double *x0, int num_starts, const double *lb, const double *ub,
+                             const bore_lbfgsb_opts *opts, const double *x, const double *fun, const double *jac,
+                             const int32_t *info, BoxArgs &box, int *nbd, lbfgsb::Options &opt) {
   if (!desc || !theta || !x0 || !lb || !ub || !opts || !x || !fun || !jac || !info)
     return fail(BORE_E_INVALID, "lbfgsb_minimize: null pointer");
   if (n_models < 1) return fail(BORE_E_INVALID, "n_models must be >= 1 (got %d)", n_models);
@@ -1144,17 +1158,28 @@ static int lbfgsb_build(const bore_mlp_desc *desc, int n_models, const float *th
     if (lo && up && lb[d] > ub[d])
       return fail(BORE_E_INVALID,
                   "LBFGSB - one of the lower bounds is greater than an upper bound.");
-    a.nbd[d] = lo && up ? 2 : lo ? 1 : up ? 3 : 0;
-    a.box.lo[d] = lo ? lb[d] : 0.0;
-    a.box.hi[d] = up ? ub[d] : 0.0;
+    nbd[d] = lo && up ? 2 : lo ? 1 : up ? 3 : 0;
+    box.lo[d] = lo ? lb[d] : 0.0;
+    box.hi[d] = up ? ub[d] : 0.0;
   }
-  const int m = opts->maxcor;
-  a.opt.m = m;
-  a.opt.factr = opts->ftol / 2.220446049250313e-16;
-  a.opt.pgtol = opts->gtol;
-  a.opt.maxiter = opts->maxiter;
-  a.opt.maxfun = opts->maxfun;
-  a.opt.maxls = opts->maxls;
+  opt.m = opts->maxcor;
+  opt.factr = opts->ftol / 2.220446049250313e-16;
+  opt.pgtol = opts->gtol;
+  opt.maxiter = opts->maxiter;
+  opt.maxfun = opts->maxfun;
+  opt.maxls = opts->maxls;
+  return 0;
+}
+
+static int lbfgsb_build(const bore_mlp_desc *desc, int n_models, const float *theta,
+                        int transform, int negate, const double *x0, int num_starts,
+                        const double *lb, const double *ub, const bore_lbfgsb_opts *opts, double *x,
+                        double *fun, double *jac, int32_t *info, LbfgsbArgs &a, size_t &lds_floats,
+                        int &flavour_out, int &blocks_out, int *waves_out = nullptr) {
+  if (const int rc = lbfgsb_check_args(desc, n_models, theta, transform, x0, num_starts, lb, ub, opts, x, fun, jac, info,
+                                       a.box, a.nbd, a.opt))
+    return rc;
+  const int D = desc->input_dim, m = a.opt.m;
   // per-problem LDS block: fp64 workspace | int workspace (8-byte aligned); the scalar
   // State lives in registers
   const size_t state_f = 0;

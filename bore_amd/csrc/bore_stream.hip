@@ -3,7 +3,10 @@
 // 512-512-512 -- and pass through LDS in panels.  Serves bore_mlp_forward, bore_mlp_evaluate,
 // bore_mlp_value_and_input_grad and bore_mlp_fit; an entry point comes here exactly when its own LDS
 // check refuses the network for capacity (or BORE_STREAM=1 asks for it: tests run both flavours on
-// the same inputs).
+// the same inputs).  The acquisition side has entry points of its own, which stream ANY float32 network
+// within the bounds: bore_stream_screen_topk / bore_stream_sample_screen_topk (the forward pass over the
+// candidates, then the selection stage of bore_argmax.hip) and bore_stream_lbfgsb_minimize (lbfgsb.h's state
+// machines, one problem per wave, around the value + input-gradient pass of this file).
 //
 // Every matrix product of the path is one routine, stream_gemm: C[M x N] = sum_r A(i, r) B(r, j) with
 // both operands in global memory, either of them read transposed.  A 64 x 128 output tile at a time:
@@ -24,6 +27,7 @@
 #include <cstdlib>
 
 #include "host_common.h"
+#include "lbfgsb.h"
 #include "mlp_device.h"
 #include "mlp_math.h"
 
@@ -226,6 +230,29 @@ struct StreamRowArgs {
   long long ws_stride;  // floats per workgroup
 };
 
+// Value and input gradient of T(sign f(x)) for the nr rows of the tile whose inputs sit in A_0: the forward pass,
+// the objective's value -- row r's into vals[r] -- and output delta, the backward pass down to D_0.  Called by the
+// whole workgroup after a barrier behind the writes of A_0; ends with a barrier (stream_gemm's), after which D_0 and
+// vals are visible to every wave.  ONE definition of the sequence for the rows kernel and the restart kernel below:
+// their values and gradients are the same bits.
+__device__ __forceinline__ void stream_value_and_grad(StreamLds &S, const MlpLayout &L, const float *th, float *ws,
+                                                      const int nr, const int transform, const float sign,
+                                                      const float *An, float *vals) {
+  const int tid = threadIdx.x, n = L.n_layers;
+  stream_forward<false>(S, L, th, ws, nr, false);
+  float *Dn = ws + SROWS * (S.pre[n + 1] + S.pre[n]);
+  if (tid < nr) {
+    const float f = An[tid];
+    const float u = sign * f;
+    float T, dT;
+    objective_transform(transform, u, T, dT);
+    vals[tid] = T;
+    Dn[tid] = sign * dT * act_grad(L.act[n], f);
+  }
+  __syncthreads();
+  for (int l = n; l >= 1; --l) stream_backward_layer(S, L, th, ws, nr, l);
+}
+
 template <bool WITH_GRAD>
 __global__ __launch_bounds__(BORE_THREADS) void stream_rows_kernel(const StreamRowArgs a) {
   __shared__ StreamLds S;
@@ -246,26 +273,244 @@ __global__ __launch_bounds__(BORE_THREADS) void stream_rows_kernel(const StreamR
       A0[i] = WITH_GRAD ? (float)a.Xd[xoff + row0 * D + i]  // Keras autocast fp64 -> fp32
                         : a.Xf[xoff + row0 * D + i];
     __syncthreads();
-    stream_forward<false>(S, L, th, ws, nr, false);
     if constexpr (!WITH_GRAD) {
+      stream_forward<false>(S, L, th, ws, nr, false);
       if (tid < nr) out[row0 + tid] = An[tid];
     } else {
-      float *Dn = ws + SROWS * (S.pre[n + 1] + S.pre[n]);
-      if (tid < nr) {
-        const float f = An[tid];
-        const float u = a.sign * f;
-        float T, dT;
-        objective_transform(a.transform, u, T, dT);
-        out[row0 + tid] = T;
-        Dn[tid] = a.sign * dT * act_grad(L.act[n], f);
-      }
-      __syncthreads();
-      for (int l = n; l >= 1; --l) stream_backward_layer(S, L, th, ws, nr, l);
+      stream_value_and_grad(S, L, th, ws, nr, a.transform, a.sign, An, out + row0);
       const float *D0 = ws + SROWS * S.pre[n + 1];
       double *grad = a.grad + (model * a.n_rows + row0) * D;
       for (int i = tid; i < nr * D; i += nthr) grad[i] = (double)D0[i];
     }
     __syncthreads();  // (the next tile overwrites the workspace)
+  }
+}
+
+// ---------------------------------------------------------------------------
+// screening: the forward pass over fp64 candidates (in memory, or row i of bore_uniform_candidates' counter stream
+// recomputed where it is read) into a prediction buffer, then one selection workgroup per model -- the selection
+// stage of bore_argmax.hip (screen_select) with an LDS carve of its own: keys and, sampled, the box; no theta.
+// ---------------------------------------------------------------------------
+struct StreamSampleArgs {
+  unsigned long long seed;
+  long long model0, draw;
+  int sampled;
+  BoxArgs box;
+};
+
+// Candidate element (row, d) of `model` in fp64: read, or recomputed exactly as candidates_kernel writes it.
+struct StreamCandidates {
+  const double *X;
+  const double *blo, *bhi;  // LDS copy of the box (indexed per lane)
+  unsigned long long cbase;
+  int D, sampled;
+  __device__ __forceinline__ double operator()(const long long row, const int d) const {
+    if (sampled) {
+      const long long i = row * D + d;
+      const unsigned long long r = mix64(cbase + 0x8CB92BA72F3D8DD7ULL * (unsigned long long)(i + 1));
+      const double u = (double)(r >> 11) * (1.0 / 9007199254740992.0);
+      return blo[d] + (bhi[d] - blo[d]) * u;
+    }
+    return X[row * D + d];
+  }
+};
+
+__device__ __forceinline__ StreamCandidates stream_candidates(const StreamSampleArgs &sp, const double *X,
+                                                              const long long n_samples, const int x_shared, const int D,
+                                                              double *box_lds) {
+  const long long model = blockIdx.x;
+  StreamCandidates c;
+  c.D = D;
+  c.sampled = sp.sampled;
+  c.X = sp.sampled ? nullptr : X + (x_shared ? 0 : model * n_samples * D);
+  c.blo = box_lds;
+  c.bhi = box_lds + D;
+  c.cbase = sp.sampled ? candidate_base(sp.seed, sp.model0 + model, sp.draw) : 0ULL;
+  if (sp.sampled && (int)threadIdx.x < D) {
+    box_lds[threadIdx.x] = sp.box.lo[threadIdx.x];
+    box_lds[D + threadIdx.x] = sp.box.hi[threadIdx.x];
+  }
+  __syncthreads();
+  return c;
+}
+
+// The rows kernel's forward form (its geometry and workspace: StreamRowArgs, n_rows = the candidates, Xd = their
+// rows) with A_0 filled from the fp64 candidates.
+__global__ __launch_bounds__(BORE_THREADS) void stream_screen_pred_kernel(const StreamRowArgs a, const StreamSampleArgs sp) {
+  __shared__ StreamLds S;
+  __shared__ double box_lds[2 * BORE_DIM_MAX];
+  const MlpLayout &L = stream_begin(S, a.L);
+  const int tid = threadIdx.x, nthr = blockDim.x;
+  const long long model = blockIdx.x;
+  const int n = L.n_layers, D = L.w[0];
+  const StreamCandidates cand = stream_candidates(sp, a.Xd, a.n_rows, a.x_shared, D, box_lds);
+  const float *th = a.theta + model * L.P;
+  float *ws = a.ws + (model * gridDim.y + blockIdx.y) * a.ws_stride;
+  float *out = a.out + model * a.n_rows;
+  const int n_tiles = (int)((a.n_rows + SROWS - 1) / SROWS);  // (n_rows <= BORE_STREAM_MAX_SAMPLES)
+  float *A0 = ws, *An = ws + SROWS * S.pre[n];
+  for (int t = blockIdx.y; t < n_tiles; t += gridDim.y) {
+    const int row0 = t * SROWS;
+    const int nr = min(SROWS, (int)a.n_rows - row0);
+    for (int i = tid; i < nr * D; i += nthr) {
+      const int r = i / D;
+      A0[i] = (float)cand(row0 + r, i - r * D);  // Keras autocast fp64 -> fp32
+    }
+    __syncthreads();
+    stream_forward<false>(S, L, th, ws, nr, false);
+    if (tid < nr) out[row0 + tid] = An[tid];
+    __syncthreads();  // (the next tile overwrites the workspace)
+  }
+}
+
+struct StreamSelectArgs {
+  const double *X;
+  const float *pred;
+  double *x0;
+  int *idx;
+  long long n_samples;
+  int x_shared, R, n_pad, D;
+};
+
+__global__ __launch_bounds__(BORE_THREADS) void stream_select_kernel(const StreamSelectArgs a, const StreamSampleArgs sp) {
+  extern __shared__ float smem[];
+  __shared__ double box_lds[2 * BORE_DIM_MAX];
+  const long long model = blockIdx.x;
+  // (the keys are 8-byte values: the dynamic region may start on a 4-byte boundary behind the static one)
+  unsigned long long *keys =
+      reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(smem) + ((8 - ((size_t)smem & 7)) & 7));
+  const StreamCandidates cand = stream_candidates(sp, a.X, a.n_samples, a.x_shared, a.D, box_lds);
+  const int tid = threadIdx.x, nthr = blockDim.x;
+  screen_keys_from_pred(tid, nthr, keys, a.pred + model * a.n_samples, (int)a.n_samples);
+  screen_select(tid, nthr, keys, (int)a.n_samples, a.n_pad, a.R, a.D, a.idx + model * a.R,
+                a.x0 + model * (long long)a.R * a.D, cand);
+}
+
+// ---------------------------------------------------------------------------
+// restarts: bound-constrained L-BFGS-B (lbfgsb.h) around the streamed value + input gradient.  Grid (model, workgroups
+// of the model).  One problem per wave at a time, all 64 lanes on it (lbfgsb::Coop); wave w of workgroup b runs the
+// model's problems (b + k gridDim.y) * waves + w, k = 0, 1, .. one after another.  A ROUND: every wave with a live
+// problem advances its state machine to the next request for f and g (finishing problems and taking the next on the
+// way) and puts the point into ITS row of A_0; then the whole workgroup runs ONE value + gradient pass over the
+// `waves` rows (stream_value_and_grad: the rows kernel's sequence, the same bits), and every wave takes f and g of
+// its row.  stream_gemm is full of barriers, so whether a round's pass runs is ONE workgroup-uniform value -- the
+// waves' requests, OR-ed through LDS behind a barrier -- and every wave, with or without a problem, runs every pass
+// until that value is 0 or the round cap (from maxfun, as lbfgsb_body's) is reached.  Rows of waves without a
+// request keep their last point (zeros at first): finite, and no row's bits depend on its neighbours.  The
+// optimiser's vectors stay in LDS (LB_LANES_SYNC waits for LDS alone); the points, values and gradients cross
+// global memory between waves of ONE workgroup, handed over by __syncthreads().  No workgroup waits for another.
+// ---------------------------------------------------------------------------
+struct StreamLbfgsbArgs {
+  MlpLayout L;
+  const float *theta;
+  const double *x0;
+  double *x, *fun, *jac;
+  int *info;
+  BoxArgs box;
+  int nbd[BORE_DIM_MAX];
+  lbfgsb::Options opt;
+  int R, transform, waves;  // waves: how many of the four hold a problem (the workspaces that fit LDS)
+  long long max_rounds;
+  float sign;
+  float *ws;
+  long long ws_stride;  // floats per workgroup
+  // dynamic LDS (float offsets from its 16-byte aligned start): box | vote | per wave: State, fp64, int workspaces
+  int o_box, o_vote, o_prob, prob_floats, o_dw, o_iw;
+};
+
+__global__ __launch_bounds__(BORE_THREADS) void stream_lbfgsb_kernel(const StreamLbfgsbArgs a) {
+  __shared__ StreamLds S;
+  extern __shared__ float smem[];
+  const MlpLayout &L = stream_begin(S, a.L);
+  const int tid = threadIdx.x;
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+  const long long model = blockIdx.x;
+  const int n = L.n_layers, D = L.w[0], NW = a.waves;
+  const float *th = a.theta + model * L.P;
+  float *ws = a.ws + (model * gridDim.y + blockIdx.y) * a.ws_stride;
+  float *A0 = ws, *An = ws + SROWS * S.pre[n];
+  const float *D0 = ws + SROWS * S.pre[n + 1];
+  // (fp64 LDS reads merge into ds_read_b128: every base on a 16-byte boundary, lbfgsb.h)
+  float *dyn = reinterpret_cast<float *>(reinterpret_cast<char *>(smem) + ((16 - ((size_t)smem & 15)) & 15));
+  double *blo = reinterpret_cast<double *>(dyn + a.o_box), *bhi = blo + ((D + 1) & ~1);
+  int *bnbd = reinterpret_cast<int *>(bhi + ((D + 1) & ~1));
+  int *vote = reinterpret_cast<int *>(dyn + a.o_vote);
+  float *slot = dyn + a.o_prob + (size_t)(wv < NW ? wv : 0) * a.prob_floats;
+  lbfgsb::State *parked = reinterpret_cast<lbfgsb::State *>(slot);
+  const lbfgsb::Work wk = lbfgsb::make_work(reinterpret_cast<double *>(slot + a.o_dw),
+                                            reinterpret_cast<int *>(slot + a.o_iw), D, a.opt.m);
+  const lbfgsb::Coop cp{lane, 64};
+  if (tid < D) {
+    blo[tid] = a.box.lo[tid];
+    bhi[tid] = a.box.hi[tid];
+    bnbd[tid] = a.nbd[tid];
+  }
+  for (int i = tid; i < BORE_THREADS / 64 * D; i += BORE_THREADS) A0[i] = 0.f;  // (rows of waves that never ask)
+  __syncthreads();
+
+  lbfgsb::State st;
+  int k = 0;           // problems this wave has taken
+  long long q = 0;     // the live one: x0 / x / fun / jac / info of restart q of the model
+  bool live = false;
+  // the wave's next problem, if the model has one left for it: a zeroed workspace (what the optimiser counts on), init
+  auto take = [&]() {
+    q = ((long long)blockIdx.y + (long long)k * gridDim.y) * NW + wv;
+    ++k;
+    live = wv < NW && q < a.R;
+    if (!live) return;
+    float4 *b4 = reinterpret_cast<float4 *>(slot);
+    for (int i = lane; i < a.prob_floats / 4; i += 64) b4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    wave_lds_sync();
+    lbfgsb::lbfgsb_init(st, wk, D, a.opt.m, a.x0 + (model * a.R + q) * D, blo, bhi, bnbd, cp);
+    wave_lds_sync();
+  };
+  auto report = [&]() {  // bore_lbfgsb_minimize's layout and semantics
+    const long long p = model * a.R + q;
+    for (int d = lane; d < D; d += 64) {
+      a.x[p * D + d] = wk.x[d];
+      a.jac[p * D + d] = wk.g[d];
+    }
+    if (lane == 0) {
+      a.fun[p] = st.f;
+      int *inf = a.info + p * 5;
+      inf[0] = st.nit; inf[1] = st.nfev; inf[2] = st.status; inf[3] = st.task; inf[4] = st.msg;
+    }
+  };
+  take();
+  for (long long round = 0; round < a.max_rounds; ++round) {
+    int need = 0;
+    while (live) {  // (wave-uniform: the 64 lanes hold the same State)
+      const int rc = __builtin_amdgcn_readfirstlane(lbfgsb::lbfgsb_advance<true>(st, wk, blo, bhi, bnbd, a.opt, cp));
+      if (rc == lbfgsb::LB_NEED_FG) {
+        for (int d = lane; d < D; d += 64) A0[wv * D + d] = (float)wk.x[d];  // Keras autocast fp64 -> fp32
+        need = 1;
+        break;
+      }
+      report();
+      take();
+    }
+    // (the State rests in LDS over the pass: stream_gemm wants the registers)
+    if (need) *parked = st;
+    if (lane == 0) vote[wv] = need;
+    __syncthreads();  // the votes; the points in A_0
+    if (!__builtin_amdgcn_readfirstlane(vote[0] | vote[1] | vote[2] | vote[3])) break;  // (ONE value for the workgroup)
+    stream_value_and_grad(S, L, th, ws, BORE_THREADS / 64, a.transform, a.sign, An, An);  // (A_n: f, then T(sign f))
+    if (need) {
+      st = *parked;
+      st.f = (double)An[wv];
+      for (int d = lane; d < D; d += 64) wk.g[d] = (double)D0[wv * D + d];
+      wave_lds_sync();
+    }
+  }
+  // The round cap (cannot happen with a sane cap): what is left is REPORTED, unoptimised, with status 2 -- never dropped.
+  while (live) {
+    if (st.stage != lbfgsb::S_FINISHED) {
+      st.status = 2;
+      st.task = lbfgsb::T_STOP;
+      st.msg = lbfgsb::M_MAXFUN;
+    }
+    report();
+    take();
   }
 }
 
@@ -616,4 +861,154 @@ extern "C" int bore_mlp_streamed(const bore_mlp_desc *desc) {
   if (mask)  // (refused by the LDS flavours: inside the streamed flavour's bounds, or the bound by name)
     if (const int rc = stream_bounds(desc, &L)) return rc;
   return mask;
+}
+
+// ---- acquisition for streamed networks: screening and restarts -------------------------------------------------------
+// What the three entry points share: any float32 network within stream_bounds (one that fits LDS as well: no switch),
+// never batch mode.  No HIP call.
+static int stream_acq_bounds(const char *who, const bore_mlp_desc *desc, int n_models, const float *theta, MlpLayout *L) {
+  if (!desc || !theta) return fail(BORE_E_INVALID, "%s: null pointer", who);
+  if (n_models < 1) return fail(BORE_E_INVALID, "n_models must be >= 1 (got %d)", n_models);
+  if (g_batch) return fail(BORE_E_UNSUPPORTED, "%s: batch mode (bore_set_batch) keeps the network in LDS", who);
+  if (const int rc = stream_bounds(desc, L)) return rc;
+  if (L->w[L->n_layers] != 1) return fail(BORE_E_INVALID, "%s: the last Dense layer must have 1 unit", who);
+  return 0;
+}
+
+static int stream_screen(const char *who, const bore_mlp_desc *desc, int n_models, const float *theta,
+                         const double *X_init, const SampleSpec *spec, int64_t n_samples, int x_shared, int num_starts,
+                         double *x0, int32_t *idx, float *pred, void *stream) {
+  StreamRowArgs a;
+  if (const int rc = stream_acq_bounds(who, desc, n_models, theta, &a.L)) return rc;
+  const int D = a.L.w[0];
+  if (spec && D > BORE_DIM_MAX)
+    return fail(BORE_E_UNSUPPORTED, "%s: the sampled form takes D <= BORE_DIM_MAX = %d (got %d)", who, BORE_DIM_MAX, D);
+  if ((!X_init && !spec) || !x0 || !idx || (spec && (!spec->low || !spec->high)))
+    return fail(BORE_E_INVALID, "%s: null pointer", who);
+  if (n_samples < 1) return fail(BORE_E_INVALID, "%s: n_samples out of range", who);
+  if (num_starts < 1 || num_starts > n_samples)
+    return fail(BORE_E_INVALID, "%s: need 1 <= num_starts <= n_samples", who);
+  if (n_samples > BORE_STREAM_MAX_SAMPLES)
+    return fail(BORE_E_UNSUPPORTED,
+                "%s: the selection ranks n_samples <= BORE_STREAM_MAX_SAMPLES = %d sort keys in one workgroup's LDS "
+                "(got %lld)", who, BORE_STREAM_MAX_SAMPLES, (long long)n_samples);
+  int n_pad = 1;
+  while (n_pad < n_samples) n_pad <<= 1;
+  StreamSampleArgs sp;
+  sp.sampled = spec != nullptr;
+  sp.seed = 0; sp.model0 = 0; sp.draw = 0;
+  if (spec) {
+    sp.seed = spec->seed; sp.model0 = spec->model_index0; sp.draw = spec->draw_index;
+    for (int d = 0; d < D; ++d) {
+      sp.box.lo[d] = spec->low[d];
+      sp.box.hi[d] = spec->high[d];
+    }
+  }
+  // the predictions: the rows kernel's geometry (stream_rows)
+  a.theta = theta; a.Xf = nullptr; a.Xd = X_init; a.grad = nullptr;
+  a.n_rows = n_samples; a.x_shared = x_shared; a.transform = 0; a.sign = 1.f;
+  a.ws_stride = (long long)stream_tile_floats(a.L);
+  long long gy = (n_samples + SROWS - 1) / SROWS;
+  const long long cap = (2 * device_cus() + n_models - 1) / n_models;
+  if (gy > cap) gy = cap;
+  const long long by_bytes = STREAM_WS_BYTES / ((long long)n_models * a.ws_stride * (long long)sizeof(float));
+  if (gy > by_bytes) gy = by_bytes;
+  if (gy < 1) gy = 1;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t ws_floats = (size_t)n_models * gy * a.ws_stride;
+  const size_t pred_floats = pred ? 0 : (size_t)n_models * n_samples;
+  float *buf = nullptr;
+  HIP_TRY(hipMallocAsync((void **)&buf, (ws_floats + pred_floats) * sizeof(float), st));
+  a.ws = buf;
+  a.out = pred ? pred : buf + ws_floats;
+  StreamSelectArgs sel;
+  sel.X = X_init; sel.pred = a.out; sel.x0 = x0; sel.idx = idx;
+  sel.n_samples = n_samples; sel.x_shared = x_shared; sel.R = num_starts; sel.n_pad = n_pad; sel.D = D;
+  const size_t key_bytes = 8 * ((size_t)n_pad + 32) + 8;
+  int rc = allow_lds(stream_select_kernel, key_bytes);
+  if (rc == 0) {
+    hipLaunchKernelGGL(stream_screen_pred_kernel, dim3(n_models, (unsigned)gy), dim3(BORE_THREADS), 0, st, a, sp);
+    hipLaunchKernelGGL(stream_select_kernel, dim3(n_models), dim3(BORE_THREADS), key_bytes, st, sel, sp);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) rc = fail(BORE_E_HIP, "%s: %s", who, hipGetErrorString(e));
+  }
+  (void)hipFreeAsync(buf, st);
+  return rc;
+}
+
+extern "C" int bore_stream_screen_topk(const bore_mlp_desc *desc, int n_models, const float *theta,
+                                       const double *X_init, int64_t n_samples, int x_shared, int num_starts,
+                                       double *x0, int32_t *idx, float *pred, void *stream) {
+  if (!X_init) return fail(BORE_E_INVALID, "stream_screen_topk: null pointer");
+  return stream_screen("stream_screen_topk", desc, n_models, theta, X_init, nullptr, n_samples, x_shared, num_starts,
+                       x0, idx, pred, stream);
+}
+
+extern "C" int bore_stream_sample_screen_topk(const bore_mlp_desc *desc, int n_models, const float *theta, uint64_t seed,
+                                              int64_t model_index0, int64_t draw_index, int64_t n_samples,
+                                              const double *low, const double *high, int num_starts, double *x0,
+                                              int32_t *idx, float *pred, void *stream) {
+  const SampleSpec spec{seed, model_index0, draw_index, low, high};
+  return stream_screen("stream_sample_screen_topk", desc, n_models, theta, nullptr, &spec, n_samples, 0, num_starts, x0,
+                       idx, pred, stream);
+}
+
+extern "C" int bore_stream_lbfgsb_minimize(const bore_mlp_desc *desc, int n_models, const float *theta, int transform,
+                                           int negate, const double *x0, int num_starts, const double *lb,
+                                           const double *ub, const bore_lbfgsb_opts *opts, double *x, double *fun,
+                                           double *jac, int32_t *info, void *stream) {
+  static const char who[] = "stream_lbfgsb_minimize";
+  StreamLbfgsbArgs a;
+  if (const int rc = stream_acq_bounds(who, desc, n_models, theta, &a.L)) return rc;
+  const int D = a.L.w[0];
+  if (D > BORE_DIM_MAX)
+    return fail(BORE_E_UNSUPPORTED, "%s: the restarts take D <= BORE_DIM_MAX = %d (got %d)", who, BORE_DIM_MAX, D);
+  if (const int rc = lbfgsb_check_args(desc, n_models, theta, transform, x0, num_starts, lb, ub, opts, x, fun, jac, info,
+                                       a.box, a.nbd, a.opt))
+    return rc;
+  // dynamic LDS beside the static StreamLds: the box, the votes, then per wave the parked State and the optimiser's
+  // fp64 and int workspaces -- every region a multiple of 16 bytes
+  const int De = (D + 1) & ~1;
+  size_t off = 0;
+  a.o_box = 0; off += 4 * (size_t)De + (((size_t)D + 3) & ~(size_t)3);
+  a.o_vote = (int)off; off += 4;
+  a.o_prob = (int)off;
+  const size_t state_f = (sizeof(lbfgsb::State) + 15) / 16 * 4;
+  const size_t dw_f = 2 * (size_t)lbfgsb::dwork_size(D, a.opt.m);
+  const size_t iw_f = ((size_t)lbfgsb::iwork_size(D) + 3) & ~(size_t)3;
+  a.o_dw = (int)state_f;
+  a.o_iw = (int)(state_f + dw_f);
+  a.prob_floats = (int)(state_f + dw_f + iw_f);
+  // (64: the static region's own alignment and the 16 bytes the kernel may skip to align the dynamic one)
+  const size_t room = (size_t)BORE_LDS_BYTES - sizeof(StreamLds) - 64 - off * 4;
+  int waves = (int)(room / ((size_t)a.prob_floats * 4));
+  if (waves > BORE_THREADS / 64) waves = BORE_THREADS / 64;
+  if (waves < 1)
+    return fail(BORE_E_UNSUPPORTED,
+                "%s: one problem's workspace (%zu B at D = %d, maxcor = %d) does not fit the %zu B of LDS beside the "
+                "streamed kernels' panels: lower maxcor", who, (size_t)a.prob_floats * 4, D, a.opt.m, room);
+  a.waves = waves;
+  const size_t lds_bytes = (off + (size_t)waves * a.prob_floats) * 4 + 16;
+  a.theta = theta; a.x0 = x0; a.x = x; a.fun = fun; a.jac = jac; a.info = info;
+  a.R = num_starts; a.transform = transform; a.sign = negate ? -1.f : 1.f;
+  // a model's restarts in groups of `waves`, a workgroup per group -- fewer, each walking several groups, when the
+  // workspaces of all would take more than STREAM_WS_BYTES
+  a.ws_stride = (long long)stream_tile_floats(a.L);
+  const long long groups = ((long long)num_starts + waves - 1) / waves;
+  long long gy = groups;
+  const long long by_bytes = STREAM_WS_BYTES / ((long long)n_models * a.ws_stride * (long long)sizeof(float));
+  if (gy > by_bytes) gy = by_bytes;
+  if (gy > 65535) gy = 65535;
+  if (gy < 1) gy = 1;
+  // every round serves one request of every live problem: a wave's problems, one after another, each within the
+  // optimiser's own limit (lbfgsb_build's cap)
+  a.max_rounds = ((groups + gy - 1) / gy) * ((long long)opts->maxfun + opts->maxls + 64);
+  hipStream_t st = (hipStream_t)stream;
+  if (const int rc = allow_lds(stream_lbfgsb_kernel, lds_bytes)) return rc;
+  HIP_TRY(hipMallocAsync((void **)&a.ws, (size_t)n_models * gy * a.ws_stride * sizeof(float), st));
+  hipLaunchKernelGGL(stream_lbfgsb_kernel, dim3(n_models, (unsigned)gy), dim3(BORE_THREADS), lds_bytes, st, a);
+  const hipError_t e = hipGetLastError();
+  (void)hipFreeAsync(a.ws, st);
+  if (e != hipSuccess) return fail(BORE_E_HIP, "streamed restart kernel: %s", hipGetErrorString(e));
+  return 0;
 }

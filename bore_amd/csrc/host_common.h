@@ -38,8 +38,8 @@ inline int check_transform(const char *who, int transform) {
 // What the entry points WITHOUT a streamed flavour (bore_stream.hip) tell the owner of a network too large for LDS.
 static const char kStreamedElsewhere[] =
     "this entry point keeps the whole network in LDS -- forward, evaluate, value + input gradient and fit stream "
-    "such float32 networks from global memory, and the model API runs their restarts through the lock-step "
-    "L-BFGS-B around the streamed kernels";
+    "such float32 networks from global memory, the bore_stream_* entry points screen and restart on them, and what "
+    "those refuse the model API runs through the lock-step L-BFGS-B around the streamed kernels";
 
 // Raise the kernel's dynamic-LDS limit to `bytes` (default cap is 64 KiB).
 // The attribute only ever needs to grow: one runtime call per kernel per new high-water mark

@@ -22,7 +22,9 @@ from .transforms import identity, resolve
 #:     same algorithm, constants and stopping rules as SciPy's, fp64; on the trained classifiers
 #:     of every BASELINE config its pick is SciPy's, tests/test_gpu_agreement.py).  A request
 #:     the kernel does not take (more than 64 input dimensions, ...) falls back to "lockstep"
-#:     with a warning.
+#:     with a warning.  A network too large for one workgroup's LDS runs the same optimiser around
+#:     the streamed kernels (bore_stream_lbfgsb_minimize); what that refuses goes to "lockstep"
+#:     silently, the route such a model had before.
 #: "lockstep": SciPy's own L-BFGS-B state machines on the host, all restarts sharing one
 #:     batched f/g launch per round (results bit-identical to "sequential"): the reference mode
 #:     the device optimiser is checked against.
@@ -98,8 +100,9 @@ class MaximizableMixin:
         self._ensure_built(X0)
         x0 = torch.from_numpy(np.ascontiguousarray(X0, dtype=np.float64)[None]).to(self.theta.device)
         tr = self._func_min.transform
-        x, fun, jac, info = ops.lbfgsb_minimize(self._desc, self.theta, x0, low, high, tr.name,
-                                                tr.negate, **options)
+        # (a network too large for one workgroup's LDS: the same optimiser around the streamed kernels)
+        restarts = ops.stream_lbfgsb_minimize if self._streamed() else ops.lbfgsb_minimize
+        x, fun, jac, info = restarts(self._desc, self.theta, x0, low, high, tr.name, tr.negate, **options)
         x, fun, jac, info = (t[0] for t in ops.lbfgsb_results_to_host(x, fun, jac, info))
         return self._results(x, fun, jac, info, range(len(X0)))
 
@@ -145,12 +148,15 @@ class MaximizableMixin:
         Xd = torch.empty((num_samples, dim), dtype=torch.float64, device=dev)
         Xd.copy_(xs, non_blocking=True)
         st[4].record()
-        x0, idx, pred = ops.screen_topk(self._desc, self.theta, Xd, num_starts, want_pred=True)
+        streamed = self._streamed()              # (too large for one workgroup's LDS: the streamed kernels' forms)
+        screen = ops.stream_screen_topk if streamed else ops.screen_topk
+        restarts = ops.stream_lbfgsb_minimize if streamed else ops.lbfgsb_minimize
+        x0, idx, pred = screen(self._desc, self.theta, Xd, num_starts, want_pred=True)
         st[0][:num_samples].copy_(pred[0], non_blocking=True)
         st[1][:num_starts].copy_(idx[0], non_blocking=True)
         st[2].record()
         tr = self._func_min.transform
-        x, fun, jac, info = ops.lbfgsb_minimize(self._desc, self.theta, x0, lo, hi, tr.name, tr.negate, **options)
+        x, fun, jac, info = restarts(self._desc, self.theta, x0, lo, hi, tr.name, tr.negate, **options)
         st[2].synchronize()                       # (fit + screening are done; the restarts are running)
         f_init = -st[0][:num_samples].numpy()
         picks = st[1][:num_starts].numpy()
@@ -163,9 +169,11 @@ class MaximizableMixin:
 
     def _streamed(self, x=None):
         """Does value + input gradient of this model run on the streamed kernels (a float32 network too large for
-        one workgroup's LDS, ``ops.mlp_streamed``)?  The in-kernel screening and restarts keep the network in LDS,
-        so for such a model screening is ``predict`` + ``argpartition`` and the restarts are the lock-step L-BFGS-B
-        around the streamed f/g kernel: its designed route, no warning."""
+        one workgroup's LDS, ``ops.mlp_streamed``)?  Screening and restarts of such a model run on the streamed
+        kernels' own forms (``ops.stream_screen_topk``, ``ops.stream_lbfgsb_minimize``).  A request those refuse --
+        more than 64 input dimensions, more candidates than one workgroup ranks -- takes ``predict`` +
+        ``argpartition`` and the lock-step L-BFGS-B around the streamed f/g kernel: the model's designed fallback,
+        no warning."""
         from . import _lib, ops
         if getattr(self, "_desc", None) is None and x is not None and hasattr(self, "_ensure_built"):
             self._ensure_built(x)
@@ -179,17 +187,19 @@ class MaximizableMixin:
 
     def _minimize_from(self, X0, bounds, method, options):
         assert self.restart_mode in RESTART_MODES, self.restart_mode
-        if method == "L-BFGS-B" and self.restart_mode == "device" and not self._streamed(X0):
+        if method == "L-BFGS-B" and self.restart_mode == "device":
             from ._lib import UnsupportedError
+            streamed = self._streamed(X0)
             try:
                 if self._func_min.transform.name is None:
                     raise UnsupportedError("a callable transform runs on the host")
                 return self._minimize_on_device(X0, bounds, dict(options or {}))
             except UnsupportedError as e:
                 import warnings
-                warnings.warn(f"restart_mode='device' cannot take this request ({e}); running "
-                              "SciPy's L-BFGS-B on the host around the f/g kernel instead",
-                              RuntimeWarning, stacklevel=3)
+                if not streamed:             # (a streamed model: the lock-step route is its designed fallback)
+                    warnings.warn(f"restart_mode='device' cannot take this request ({e}); running "
+                                  "SciPy's L-BFGS-B on the host around the f/g kernel instead",
+                                  RuntimeWarning, stacklevel=3)
         if (method == "L-BFGS-B" and self.restart_mode in ("device", "lockstep")
                 and lockstep.available()):
             return lockstep.minimize_lockstep(self._func_min, X0, bounds=bounds,
@@ -208,7 +218,7 @@ class MaximizableMixin:
         X_init = random_state.uniform(low=low, high=high, size=(num_samples, dim))    # (ONE draw, bore/mixins.py:45-47)
         f_init = results = None
         if (self.screen_mode == "device" and self.restart_mode == "device" and method == "L-BFGS-B" and num_starts > 0
-                and self._func_min.transform.name is not None and not self._streamed(X_init)):
+                and self._func_min.transform.name is not None):
             from ._lib import UnsupportedError
             try:
                 f_init, results = self._maxima_on_device(X_init, bounds, num_starts, dict(options or {}))

@@ -184,9 +184,7 @@ def uniform_candidates(seed, n_models, n_samples, low, high, model_index0=0, dra
     return X
 
 
-def screen_topk(desc, theta, X_init, num_starts, want_pred=False):
-    """Screening of ``maxima``: predict on X_init ([L,Ns,D] or shared [Ns,D], f64) and return
-    (x0 [L,R,D] f64, idx [L,R] int32[, pred [L,Ns] f32]) for the R = num_starts best rows."""
+def _screen_topk(entry, desc, theta, X_init, num_starts, want_pred):
     L, P = theta.shape
     D = desc.input_dim
     shared = X_init.dim() == 2
@@ -197,16 +195,26 @@ def screen_topk(desc, theta, X_init, num_starts, want_pred=False):
     x0 = torch.empty((L, R, D), dtype=torch.float64, device=theta.device)
     idx = torch.empty((L, R), dtype=torch.int32, device=theta.device)
     pred = torch.empty((L, Ns), dtype=torch.float32, device=theta.device) if (want_pred or Ns >= 1024) else None
-    _lib.check(_lib.lib().bore_screen_topk(C.byref(desc), L, _lib.ptr(theta), _lib.ptr(X_init), Ns,
-                                           int(shared), R, _lib.ptr(x0), _lib.ptr(idx),
-                                           _lib.ptr(pred), _lib.stream_ptr()))
+    _lib.check(entry(C.byref(desc), L, _lib.ptr(theta), _lib.ptr(X_init), Ns, int(shared), R, _lib.ptr(x0),
+                     _lib.ptr(idx), _lib.ptr(pred), _lib.stream_ptr()))
     return (x0, idx, pred) if want_pred else (x0, idx)
 
 
-def sample_screen_topk(desc, theta, seed, n_samples, low, high, num_starts, model_index0=0,
-                       draw_index=0, want_pred=False):
-    """``uniform_candidates`` + ``screen_topk`` in one launch; the candidates are never written to
-    memory (``bore_sample_screen_topk``).  Returns (x0 [L,R,D] f64, idx [L,R] int32[, pred])."""
+def screen_topk(desc, theta, X_init, num_starts, want_pred=False):
+    """Screening of ``maxima``: predict on X_init ([L,Ns,D] or shared [Ns,D], f64) and return
+    (x0 [L,R,D] f64, idx [L,R] int32[, pred [L,Ns] f32]) for the R = num_starts best rows."""
+    return _screen_topk(_lib.lib().bore_screen_topk, desc, theta, X_init, num_starts, want_pred)
+
+
+def stream_screen_topk(desc, theta, X_init, num_starts, want_pred=False):
+    """``screen_topk`` on the streamed kernels (``bore_stream_screen_topk``): any float32 network within the streamed
+    bounds -- the ones too large for one workgroup's LDS, and smaller ones alike.  Same arguments and results; ``pred``
+    is ``mlp_forward`` of the float32-cast candidates, bit for bit."""
+    return _screen_topk(_lib.lib().bore_stream_screen_topk, desc, theta, X_init, num_starts, want_pred)
+
+
+def _sample_screen_topk(entry, desc, theta, seed, n_samples, low, high, num_starts, model_index0, draw_index,
+                        want_pred):
     L = theta.shape[0]
     D = desc.input_dim
     _chk(theta, torch.float32, (L, param_count(desc)), "theta")
@@ -218,21 +226,31 @@ def sample_screen_topk(desc, theta, seed, n_samples, low, high, num_starts, mode
     # (a prediction buffer lets the library spread the predictions of a few wide models over the
     # device: bore_argmax.hip, screen_body MODE 1 / 2; same results)
     pred = torch.empty((L, Ns), dtype=torch.float32, device=theta.device) if (want_pred or Ns >= 1024) else None
-    _lib.check(_lib.lib().bore_sample_screen_topk(
+    _lib.check(entry(
         C.byref(desc), L, _lib.ptr(theta), C.c_uint64(seed & (2**64 - 1)), int(model_index0),
         int(draw_index), Ns, lo_p, hi_p, R, _lib.ptr(x0), _lib.ptr(idx), _lib.ptr(pred),
         _lib.stream_ptr()))
     return (x0, idx, pred) if want_pred else (x0, idx)
 
 
-def lbfgsb_minimize(desc, theta, x0, low, high, transform="identity", negate=True, maxcor=10,
-                    ftol=2.2204460492503131e-09, gtol=1e-5, maxfun=15000, maxiter=15000,
-                    maxls=20):
-    """R bound-constrained L-BFGS-B minimisations of T(+-f(x)) per model, on the device.
+def sample_screen_topk(desc, theta, seed, n_samples, low, high, num_starts, model_index0=0,
+                       draw_index=0, want_pred=False):
+    """``uniform_candidates`` + ``screen_topk`` in one launch; the candidates are never written to
+    memory (``bore_sample_screen_topk``).  Returns (x0 [L,R,D] f64, idx [L,R] int32[, pred])."""
+    return _sample_screen_topk(_lib.lib().bore_sample_screen_topk, desc, theta, seed, n_samples, low, high,
+                               num_starts, model_index0, draw_index, want_pred)
 
-    x0 [L,R,D] f64; low/high: length-D host sequences (+-inf for open sides).
-    Returns (x [L,R,D] f64, fun [L,R] f64, jac [L,R,D] f64, info [L,R,5] int32) with
-    info = (nit, nfev, status, task, message) as in scipy's OptimizeResult / task tables."""
+
+def stream_sample_screen_topk(desc, theta, seed, n_samples, low, high, num_starts, model_index0=0,
+                              draw_index=0, want_pred=False):
+    """``sample_screen_topk`` on the streamed kernels (``bore_stream_sample_screen_topk``, D <= 64): the same picks,
+    bit for bit, as ``uniform_candidates`` followed by ``stream_screen_topk``."""
+    return _sample_screen_topk(_lib.lib().bore_stream_sample_screen_topk, desc, theta, seed, n_samples, low, high,
+                               num_starts, model_index0, draw_index, want_pred)
+
+
+def _lbfgsb_minimize(entry, desc, theta, x0, low, high, transform="identity", negate=True, maxcor=10,
+                     ftol=2.2204460492503131e-09, gtol=1e-5, maxfun=15000, maxiter=15000, maxls=20):
     L, P = theta.shape
     D = desc.input_dim
     _chk(theta, torch.float32, (L, param_count(desc)), "theta")
@@ -255,11 +273,32 @@ def lbfgsb_minimize(desc, theta, x0, low, high, transform="identity", negate=Tru
     info = buf[2 * n_xd + L * R:].view(torch.int32)[:L * R * 5].view(L, R, 5)
     if R == 0:
         return x, fun, jac, info
-    _lib.check(_lib.lib().bore_lbfgsb_minimize(
+    _lib.check(entry(
         C.byref(desc), L, _lib.ptr(theta), _lib.TRANSFORM[transform], int(bool(negate)),
         _lib.ptr(x0), R, lo_p, hi_p, C.byref(opts), _lib.ptr(x), _lib.ptr(fun), _lib.ptr(jac),
         _lib.ptr(info), _lib.stream_ptr()))
     return x, fun, jac, info
+
+
+def lbfgsb_minimize(desc, theta, x0, low, high, transform="identity", negate=True, maxcor=10,
+                    ftol=2.2204460492503131e-09, gtol=1e-5, maxfun=15000, maxiter=15000,
+                    maxls=20):
+    """R bound-constrained L-BFGS-B minimisations of T(+-f(x)) per model, on the device.
+
+    x0 [L,R,D] f64; low/high: length-D host sequences (+-inf for open sides).
+    Returns (x [L,R,D] f64, fun [L,R] f64, jac [L,R,D] f64, info [L,R,5] int32) with
+    info = (nit, nfev, status, task, message) as in scipy's OptimizeResult / task tables."""
+    return _lbfgsb_minimize(_lib.lib().bore_lbfgsb_minimize, desc, theta, x0, low, high, transform, negate, maxcor,
+                            ftol, gtol, maxfun, maxiter, maxls)
+
+
+def stream_lbfgsb_minimize(desc, theta, x0, low, high, transform="identity", negate=True, **options):
+    """``lbfgsb_minimize`` on the streamed kernels (``bore_stream_lbfgsb_minimize``, D <= 64): any float32 network
+    within the streamed bounds.  Same arguments, the same packed results (``lbfgsb_results_to_host``: one copy);
+    every record is the host build of the optimiser fed ``mlp_value_and_input_grad``'s streamed f and g, bit for
+    bit."""
+    return _lbfgsb_minimize(_lib.lib().bore_stream_lbfgsb_minimize, desc, theta, x0, low, high, transform, negate,
+                            **options)
 
 
 def lbfgsb_results_to_host(x, fun, jac, info):

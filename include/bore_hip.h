@@ -574,10 +574,12 @@ int bore_lstm_evaluate(const bore_lstm_desc *desc, int n_models, const float *th
  * Workspace per call, stream-ordered: the rows kernels at most 64 MiB (or one 64-row tile per model), the fit
  * 2*64*sum(widths) + (batch_size > 64: P) floats per model, plus, with perm == NULL, the drawn shuffles
  * (n_models*epochs*N ints, at most 64 MiB: BORE_E_NEEDS_PERM beyond, as for N too long to rank in LDS).  One workgroup per model in the fit: a single
- * model leaves the rest of the device idle.  The screening, restart, SVGD and engine entry points
- * keep the network in LDS and keep refusing such networks.  Additive to ABI 12.
+ * model leaves the rest of the device idle.  bore_screen_topk, bore_sample_screen_topk, bore_lbfgsb_minimize, the
+ * SVGD and the engine entry points keep the network in LDS and keep refusing such networks; screening and restarts
+ * have streamed entry points of their own (bore_stream_*, below).  Additive to ABI 12.
  * --------------------------------------------------------------------------------------------- */
 #define BORE_STREAM_MAX_UNITS 512
+#define BORE_STREAM_MAX_SAMPLES 16384 /* candidates per model the streamed screening ranks in one workgroup's LDS */
 
 /* Pure host query (ignores BORE_STREAM): which entry points would run `desc` streamed.
  *   bit 0  bore_mlp_forward / bore_mlp_evaluate
@@ -586,6 +588,35 @@ int bore_lstm_evaluate(const bore_lstm_desc *desc, int n_models, const float *th
  * 0 for a network that fits LDS and for bfloat16; BORE_E_INVALID on a bad descriptor;
  * BORE_E_UNSUPPORTED (the bound named) for a network that fits neither. */
 int bore_mlp_streamed(const bore_mlp_desc *desc);
+
+/*
+ * The acquisition side on the streamed kernels: argument lists, outputs and semantics of bore_screen_topk,
+ * bore_sample_screen_topk and bore_lbfgsb_minimize.  They take ANY float32 network within the streamed bounds --
+ * one that fits LDS as well, no BORE_STREAM switch involved -- and refuse, before any HIP call and with the bound
+ * named: bfloat16, batch mode (bore_set_batch), a width above BORE_STREAM_MAX_UNITS; the sampled screening and the
+ * restarts an input dimension above BORE_DIM_MAX; the screening n_samples above BORE_STREAM_MAX_SAMPLES.
+ *   screening  two launches on the stream: the streamed forward pass over the candidates (fp64 rows cast to fp32 as
+ *              Keras casts them, or the counter stream of bore_uniform_candidates) into `pred` -- stream-ordered
+ *              scratch when pred == NULL -- bit for bit bore_mlp_forward's values; then one workgroup per model
+ *              ranks them (descending prediction, ties to the lower row) and gathers the chosen rows in fp64.
+ *   restarts   one launch; one problem per wave at a time, up to four per workgroup (as many as have room for
+ *              their workspace in LDS beside the panels), the workgroup's pending points evaluated by one streamed
+ *              value + input-gradient pass per round.  Every record equals the host build of lbfgsb.h fed
+ *              bore_mlp_value_and_input_grad's f and g, bit for bit, whatever the geometry.  Workspace per call,
+ *              stream-ordered: one 64-row tile per workgroup, at most 64 MiB (a workgroup then walks several
+ *              groups of restarts).
+ */
+int bore_stream_screen_topk(const bore_mlp_desc *desc, int n_models, const float *theta,
+                            const double *X_init, int64_t n_samples, int x_shared, int num_starts,
+                            double *x0, int32_t *idx, float *pred, void *stream);
+int bore_stream_sample_screen_topk(const bore_mlp_desc *desc, int n_models, const float *theta,
+                                   uint64_t seed, int64_t model_index0, int64_t draw_index,
+                                   int64_t n_samples, const double *low, const double *high,
+                                   int num_starts, double *x0, int32_t *idx, float *pred, void *stream);
+int bore_stream_lbfgsb_minimize(const bore_mlp_desc *desc, int n_models, const float *theta,
+                                int transform, int negate, const double *x0, int num_starts,
+                                const double *lb, const double *ub, const bore_lbfgsb_opts *opts,
+                                double *x, double *fun, double *jac, int32_t *info, void *stream);
 
 #ifdef __cplusplus
 }
