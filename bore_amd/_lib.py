@@ -45,6 +45,7 @@ EXPORTS = [
     "bore_lstm_param_count", "bore_lstm_forward", "bore_lstm_value_and_input_grad", "bore_lstm_fit",
     "bore_lstm_evaluate", "bore_mlp_streamed",
     "bore_stream_screen_topk", "bore_stream_sample_screen_topk", "bore_stream_lbfgsb_minimize",
+    "bore_stream_svgd_optimize",
 ]
 
 
@@ -249,6 +250,7 @@ def lib():
     L.bore_stream_screen_topk.argtypes = L.bore_screen_topk.argtypes
     L.bore_stream_sample_screen_topk.argtypes = L.bore_sample_screen_topk.argtypes
     L.bore_stream_lbfgsb_minimize.argtypes = L.bore_lbfgsb_minimize.argtypes
+    L.bore_stream_svgd_optimize.argtypes = L.bore_svgd_optimize.argtypes
     for name in EXPORTS:
         if name not in ("bore_last_error", "bore_param_count", "bore_lstm_param_count", "bore_engine_size",
                         "bore_engine_destroy", "bore_set_batch"):

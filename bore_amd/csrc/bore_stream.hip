@@ -5,8 +5,9 @@
 // check refuses the network for capacity (or BORE_STREAM=1 asks for it: tests run both flavours on
 // the same inputs).  The acquisition side has entry points of its own, which stream ANY float32 network
 // within the bounds: bore_stream_screen_topk / bore_stream_sample_screen_topk (the forward pass over the
-// candidates, then the selection stage of bore_argmax.hip) and bore_stream_lbfgsb_minimize (lbfgsb.h's state
-// machines, one problem per wave, around the value + input-gradient pass of this file).
+// candidates, then the selection stage of bore_argmax.hip), bore_stream_lbfgsb_minimize (lbfgsb.h's state
+// machines, one problem per wave, around the value + input-gradient pass of this file) and bore_stream_svgd_optimize
+// (svgd_interact.h's particle interaction, one workgroup per model, around the same pass).
 //
 // Every matrix product of the path is one routine, stream_gemm: C[M x N] = sum_r A(i, r) B(r, j) with
 // both operands in global memory, either of them read transposed.  A 64 x 128 output tile at a time:
@@ -30,6 +31,7 @@
 #include "lbfgsb.h"
 #include "mlp_device.h"
 #include "mlp_math.h"
+#include "svgd_interact.h"
 
 namespace bore {
 
@@ -512,6 +514,69 @@ __global__ __launch_bounds__(BORE_THREADS) void stream_lbfgsb_kernel(const Strea
     report();
     take();
   }
+}
+
+// ---------------------------------------------------------------------------
+// SVGD batch acquisition (bore_svgd.hip's statement of it): ONE workgroup per model, every iteration of every
+// particle in one launch.  The particle state -- x, fg, grad, hist fp64 [n][D], f and zeta fp64 [n], the radix
+// select's scratch -- stays in the dynamic LDS beside the panels for the whole launch: svgd_big_kernel's carve
+// without theta and without the activation tile, and no n x n matrix for any n (svgd_interact.h forms its entries
+// on the fly: ONE definition of the interaction for both kernels).  Value and input gradient of the particles,
+// 64 at a time, are the rows kernel's sequence (stream_value_and_grad: the same bits), sign +1: SVGD climbs
+// transform(f).  The points, values and gradients cross global memory between waves of ONE workgroup, handed over
+// by __syncthreads().  No workgroup waits for another; no float atomics.
+// ---------------------------------------------------------------------------
+struct StreamSvgdArgs {
+  MlpLayout L;
+  const float *theta;
+  const double *x_init;
+  double *x_out;
+  double lo[BORE_DIM_MAX], hi[BORE_DIM_MAX];
+  int clip, n, n_iter, transform, distortion;
+  double step, alpha, eps, tau, length_scale, dparam;
+  float *ws;
+  long long ws_stride;  // floats per workgroup
+  // dynamic LDS (float offsets from its 16-byte aligned start; every region a multiple of 16 bytes)
+  int o_x, o_fg, o_grad, o_hist, o_f, o_sel;
+};
+
+__global__ __launch_bounds__(BORE_THREADS) void stream_svgd_kernel(const StreamSvgdArgs a) {
+  __shared__ StreamLds S;
+  extern __shared__ float smem[];
+  const MlpLayout &L = stream_begin(S, a.L);
+  const int tid = threadIdx.x;
+  const long long model = blockIdx.x;
+  const int nl = L.n_layers, D = L.w[0], n = a.n, nD = n * D;
+  const float *th = a.theta + model * L.P;
+  float *ws = a.ws + model * a.ws_stride;
+  float *A0 = ws, *An = ws + SROWS * S.pre[nl];
+  const float *D0 = ws + SROWS * S.pre[nl + 1];
+  float *dyn = reinterpret_cast<float *>(reinterpret_cast<char *>(smem) + ((16 - ((size_t)smem & 15)) & 15));
+  double *x = reinterpret_cast<double *>(dyn + a.o_x);
+  double *fg = reinterpret_cast<double *>(dyn + a.o_fg);
+  double *grad = reinterpret_cast<double *>(dyn + a.o_grad);
+  double *hist = reinterpret_cast<double *>(dyn + a.o_hist);
+  double *f = reinterpret_cast<double *>(dyn + a.o_f), *zeta = f + n;
+  unsigned *sel = reinterpret_cast<unsigned *>(dyn + a.o_sel);  // [256] bins + [8] scratch
+  for (int e = tid; e < nD; e += BORE_THREADS) x[e] = a.x_init[model * nD + e];
+  __syncthreads();
+  for (int it = 0; it < a.n_iter; ++it) {
+    const double gamma = svgd_gamma(x, n, D, a.length_scale, sel);
+    // value and input gradient of every particle, 64 rows of the workspace tile at a time
+    for (int c0 = 0; c0 < n; c0 += SROWS) {
+      const int nr = min(SROWS, n - c0);
+      for (int i = tid; i < nr * D; i += BORE_THREADS) A0[i] = (float)x[c0 * D + i];  // Keras autocast fp64 -> fp32
+      __syncthreads();
+      stream_value_and_grad(S, L, th, ws, nr, a.transform, 1.f, An, An);  // (A_n: f, then T(f))
+      for (int i = tid; i < nr * D; i += BORE_THREADS) fg[c0 * D + i] = (double)D0[i];
+      for (int i = tid; i < nr; i += BORE_THREADS) f[c0 + i] = (double)An[i];
+      __syncthreads();  // (the next chunk overwrites the workspace)
+    }
+    svgd_zeta(f, zeta, n, a.distortion, a.dparam);
+    svgd_drive_repulsion(x, fg, zeta, grad, n, D, gamma, a.tau);
+    svgd_step_clip(x, grad, hist, nD, D, it == 0, a.step, a.alpha, a.eps, a.clip, a.lo, a.hi);
+  }
+  for (int e = tid; e < nD; e += BORE_THREADS) a.x_out[model * nD + e] = x[e];
 }
 
 // ---------------------------------------------------------------------------
@@ -1010,5 +1075,63 @@ extern "C" int bore_stream_lbfgsb_minimize(const bore_mlp_desc *desc, int n_mode
   const hipError_t e = hipGetLastError();
   (void)hipFreeAsync(a.ws, st);
   if (e != hipSuccess) return fail(BORE_E_HIP, "streamed restart kernel: %s", hipGetErrorString(e));
+  return 0;
+}
+
+extern "C" int bore_stream_svgd_optimize(const bore_mlp_desc *desc, int n_models, const float *theta, int transform,
+                                         const double *x_init, int n_particles, const double *lb, const double *ub,
+                                         const bore_svgd_opts *opts, double *x_out, void *stream) {
+  static const char who[] = "stream_svgd_optimize";
+  StreamSvgdArgs a;
+  if (!x_init || !x_out || !opts) return fail(BORE_E_INVALID, "%s: null pointer", who);
+  if (const int rc = stream_acq_bounds(who, desc, n_models, theta, &a.L)) return rc;
+  const int D = a.L.w[0], n = n_particles;
+  if (D > BORE_DIM_MAX)
+    return fail(BORE_E_UNSUPPORTED, "%s: the box goes by value, D <= BORE_DIM_MAX = %d (got %d)", who, BORE_DIM_MAX, D);
+  if (n < 1 || n > BORE_SVGD_MAX_PARTICLES)  // (what fits is decided by the LDS check below: 32 n D bytes of state)
+    return fail(BORE_E_UNSUPPORTED, "%s: 1..%d particles per launch (got %d)", who, BORE_SVGD_MAX_PARTICLES, n);
+  if (const int rc = check_transform(who, transform)) return rc;
+  if (opts->n_iter < 0 || (opts->distortion != 0 && opts->distortion != 1))
+    return fail(BORE_E_INVALID, "%s: bad options", who);
+  if ((lb == nullptr) != (ub == nullptr)) return fail(BORE_E_INVALID, "%s: lb and ub go together", who);
+  // dynamic LDS beside the static StreamLds: svgd_big_kernel's particle state, no theta, no activation tile
+  const size_t nD2 = 2 * (((size_t)n * D + 1) & ~(size_t)1);  // floats of an [n][D] fp64 array, 16-B multiple
+  size_t off = 0;
+  a.o_x = (int)off; off += nD2;
+  a.o_fg = (int)off; off += nD2;
+  a.o_grad = (int)off; off += nD2;
+  a.o_hist = (int)off; off += nD2;
+  a.o_f = (int)off; off += 4 * (size_t)n;
+  a.o_sel = (int)off; off += SVGD_SELECT_WORDS;
+  const size_t lds_bytes = off * 4 + 16;  // (16: what the kernel may skip to align the dynamic region)
+  // (64: the static region's own alignment, as for the restarts)
+  if (sizeof(StreamLds) + 64 + lds_bytes > (size_t)BORE_LDS_BYTES)
+    return fail(BORE_E_UNSUPPORTED,
+                "%s: %d particles in %d dimensions need %zu B of LDS (> %d) beside the streamed kernels' panels: the "
+                "particle state is 32 n D bytes",
+                who, n, D, sizeof(StreamLds) + 64 + lds_bytes, BORE_LDS_BYTES);
+  // one workspace tile per model, never walked: a second geometry would be a second, untested code path
+  a.ws_stride = (long long)stream_tile_floats(a.L);
+  if ((long long)n_models * a.ws_stride * (long long)sizeof(float) > STREAM_WS_BYTES)
+    return fail(BORE_E_UNSUPPORTED,
+                "%s: %d models x one %lld B workspace tile exceed the %lld MiB a streamed call allows itself "
+                "(STREAM_WS_BYTES): fewer models per call",
+                who, n_models, a.ws_stride * (long long)sizeof(float), STREAM_WS_BYTES >> 20);
+  a.clip = lb != nullptr;
+  for (int d = 0; d < BORE_DIM_MAX; ++d) {
+    a.lo[d] = lb && d < D ? lb[d] : 0.0;
+    a.hi[d] = ub && d < D ? ub[d] : 0.0;
+  }
+  a.theta = theta; a.x_init = x_init; a.x_out = x_out;
+  a.n = n; a.n_iter = opts->n_iter; a.transform = transform; a.distortion = opts->distortion;
+  a.step = opts->step_size; a.alpha = opts->alpha; a.eps = opts->eps; a.tau = opts->tau;
+  a.length_scale = opts->length_scale; a.dparam = opts->distortion_param;
+  hipStream_t st = (hipStream_t)stream;
+  if (const int rc = allow_lds(stream_svgd_kernel, lds_bytes)) return rc;
+  HIP_TRY(hipMallocAsync((void **)&a.ws, (size_t)n_models * a.ws_stride * sizeof(float), st));
+  hipLaunchKernelGGL(stream_svgd_kernel, dim3(n_models), dim3(BORE_THREADS), lds_bytes, st, a);
+  const hipError_t e = hipGetLastError();
+  (void)hipFreeAsync(a.ws, st);
+  if (e != hipSuccess) return fail(BORE_E_HIP, "streamed SVGD kernel: %s", hipGetErrorString(e));
   return 0;
 }

@@ -265,7 +265,14 @@ class BatchMaximizableMixin(MaximizableMixin):
                 matrix and history in LDS; beyond 64 particles the matrix entries are formed on the fly);
                 float32 networks, and bfloat16 ones of the wide static shapes; what does not fit a
                 compute unit's LDS (32 n D bytes of particle state beside the network), a callable
-                transform or a user's kernel object goes to "host" with a warning;
+                transform or a user's kernel object goes to "host" with a warning.  A float32 network
+                too large for one workgroup's LDS (``_streamed``) runs the same interaction in one launch
+                around the streamed kernels (``bore_stream_svgd_optimize``: one workgroup, so one compute
+                unit, per model; the particle state in the ~105 KB of LDS beside the panels, up to 64
+                input dimensions) where that is not slower than "host", i.e. up to
+                ``stream_svgd_max_work``; beyond it, and what the kernel refuses, goes to "host" with
+                the same warning.  Models that
+                fit LDS never take the streamed kernel;
       "host"    for what the device refuses: ``_func_max`` -- value + input gradient of
                 ``transform(f(x))`` for all particles -- is one HIP launch per SVGD iteration;
                 kernel matrix, repulsion and the Adagrad step are a short float64 numpy driver
@@ -275,6 +282,12 @@ class BatchMaximizableMixin(MaximizableMixin):
                 tests/test_svgd.py) and is ~an order of magnitude faster than the host driver."""
 
     svgd_mode = "device"
+    #: a streamed model takes the one-launch kernel up to this n^2 D (particles^2 x input dimensions), the host driver
+    #: beyond: the kernel's particle interaction runs on ONE compute unit and grows with n^2 D, the host driver's
+    #: per-iteration launch and download do not.  Measured (profiles/stream/svgd_time.json, 1 000 iterations): the
+    #: kernel is 1.3 - 1.5x faster at 8 particles, even at 32 x 32 x 16 and 64 x 64 x 8, and takes 1.55x the host
+    #: driver's time at 64 x 64 x 16.  None: no limit (tools/stream_svgd_time.py measures the kernel itself).
+    stream_svgd_max_work = 64 * 64 * 8
 
     def __init__(self, transform=identity, *args, **kwargs):
         super(BatchMaximizableMixin, self).__init__(transform, *args, **kwargs)
@@ -298,7 +311,15 @@ class BatchMaximizableMixin(MaximizableMixin):
             try:
                 if self.transform.name is None:
                     raise UnsupportedError("a callable transform runs on the host")
-                out = ops.svgd_optimize(
+                # (a network too large for one workgroup's LDS: the same interaction around the streamed kernels)
+                svgd = ops.stream_svgd_optimize if self._streamed(x_init) else ops.svgd_optimize
+                work = batch_size * batch_size * dims
+                if svgd is ops.stream_svgd_optimize and self.stream_svgd_max_work is not None \
+                        and work > self.stream_svgd_max_work:
+                    raise UnsupportedError(
+                        f"{batch_size} particles in {dims} dimensions: beyond n^2 D = {self.stream_svgd_max_work} the "
+                        "one-launch kernel for networks too large for LDS is not faster than the host driver")
+                out = svgd(
                     self._desc, self.theta,
                     torch.from_numpy(np.ascontiguousarray(x_init[None])).to(self.theta.device), low,
                     high, self.transform.name, length_scale=length_scale, n_iter=n_iter,

@@ -574,9 +574,9 @@ int bore_lstm_evaluate(const bore_lstm_desc *desc, int n_models, const float *th
  * Workspace per call, stream-ordered: the rows kernels at most 64 MiB (or one 64-row tile per model), the fit
  * 2*64*sum(widths) + (batch_size > 64: P) floats per model, plus, with perm == NULL, the drawn shuffles
  * (n_models*epochs*N ints, at most 64 MiB: BORE_E_NEEDS_PERM beyond, as for N too long to rank in LDS).  One workgroup per model in the fit: a single
- * model leaves the rest of the device idle.  bore_screen_topk, bore_sample_screen_topk, bore_lbfgsb_minimize, the
- * SVGD and the engine entry points keep the network in LDS and keep refusing such networks; screening and restarts
- * have streamed entry points of their own (bore_stream_*, below).  Additive to ABI 12.
+ * model leaves the rest of the device idle.  bore_screen_topk, bore_sample_screen_topk, bore_lbfgsb_minimize,
+ * bore_svgd_optimize and the engine entry points keep the network in LDS and keep refusing such networks; screening,
+ * restarts and SVGD have streamed entry points of their own (bore_stream_*, below).  Additive to ABI 12.
  * --------------------------------------------------------------------------------------------- */
 #define BORE_STREAM_MAX_UNITS 512
 #define BORE_STREAM_MAX_SAMPLES 16384 /* candidates per model the streamed screening ranks in one workgroup's LDS */
@@ -617,6 +617,24 @@ int bore_stream_lbfgsb_minimize(const bore_mlp_desc *desc, int n_models, const f
                                 int transform, int negate, const double *x0, int num_starts,
                                 const double *lb, const double *ub, const bore_lbfgsb_opts *opts,
                                 double *x, double *fun, double *jac, int32_t *info, void *stream);
+
+/*
+ * bore_svgd_optimize on the streamed kernels: its argument list, outputs and semantics (n_iter == 0 returns x_init;
+ * lb == ub == NULL: no clipping).  ANY float32 network within the streamed bounds, one that fits LDS as well.  One
+ * launch, ONE workgroup per model -- a single model uses one compute unit -- for all n_iter iterations: the particle
+ * state (32 n_particles D bytes, plus 16 n_particles and the select's 1 KB) stays in LDS beside the panels, no
+ * n x n matrix for any n_particles; value and input gradient of the particles, 64 at a time, are
+ * bore_mlp_value_and_input_grad's streamed bits.  Particles agree with the host statement of SVGD fed those values
+ * to rounding (1e-9 after 200 iterations), not bit for bit; they do not depend on n_models or on the run.
+ * Refused before any HIP call, the bound named: bfloat16, batch mode, a width above BORE_STREAM_MAX_UNITS, an input
+ * dimension above BORE_DIM_MAX, n_particles outside 1..4096, particle state that does not fit the LDS beside the
+ * panels (about 105 KB: 395 particles at D = 8, 203 at D = 16, 52 at D = 64), and n_models x one 64-row workspace
+ * tile (2*64*sum(widths) floats) above 64 MiB -- refused, not walked.  Measured against the host statement (one
+ * launch, a download and a numpy step per iteration): profiles/stream/svgd_time.json.
+ */
+int bore_stream_svgd_optimize(const bore_mlp_desc *desc, int n_models, const float *theta, int transform,
+                              const double *x_init, int n_particles, const double *lb, const double *ub,
+                              const bore_svgd_opts *opts, double *x_out, void *stream);
 
 #ifdef __cplusplus
 }
