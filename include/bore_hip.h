@@ -494,8 +494,11 @@ void bore_engine_destroy(bore_engine *engine);
  * layer).  Loss: BCE from logits weighted by the mask and divided by ALL n*T elements (TF 2.5
  * SUM_OVER_BATCH_SIZE), plus l2 * sum(w^2) for W and b of every cell (never U) and of the head.
  * Bounds of this build: BORE_LSTM_MAX_* below, and the parameters plus one 64-sequence tile of
- * state in one CU's LDS (the plugin default D <= 32, 32 units, 2 layers fits); BORE_E_UNSUPPORTED
- * names the bound otherwise.  Additive to ABI 12.
+ * state in one CU's LDS (160 KB); BORE_E_UNSUPPORTED names the bound otherwise.  The LDS budget is
+ * the bound that binds: one layer takes at most 58 units (D = 1, T = 1), 57 at D = 2, 54 at
+ * T = 16, 50 at D = 16 and T = 16, so BORE_LSTM_MAX_UNITS itself is never reached.  The plugin
+ * default, 2 layers of 32 units, needs 151 376 B at D = 16 and T = 16 (92 % of the budget) and
+ * fits up to D = 32; a third layer of 32 units does not fit.  Additive to ABI 12.
  * --------------------------------------------------------------------------------------------- */
 #define BORE_LSTM_MAX_LAYERS 4
 #define BORE_LSTM_MAX_UNITS 64
@@ -505,7 +508,7 @@ void bore_engine_destroy(bore_engine *engine);
 typedef struct bore_lstm_desc {
   int32_t input_dim;                         /* D */
   int32_t n_layers;                          /* LSTM cells, 1..BORE_LSTM_MAX_LAYERS */
-  int32_t units;                             /* H, the same for every cell */
+  int32_t units;                             /* H, the same for every cell (LDS: <= 58, above) */
   int32_t act;                               /* enum bore_activation of the cells */
   float l2_kernel[BORE_LSTM_MAX_LAYERS + 1]; /* kernel_regularizer=l2(f) per cell; [n_layers]: the head */
   float l2_bias[BORE_LSTM_MAX_LAYERS + 1];   /* bias_regularizer=l2(f) per cell; [n_layers]: the head */

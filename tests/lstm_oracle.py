@@ -15,13 +15,18 @@ TensorFlow 2.5 (the reference's pin, setup.py:42) cannot run here, so its rules 
   accuracy  binary_accuracy on the model output (the logit) at 0.5, weighted by the mask
   fit       one permutation of the sequences per epoch; logged loss = batch losses (before each update)
             averaged with batch-size weights; Keras Adam (oracle.bore_oracle.adam_step)
+
+Every function takes ``dtype`` (default float64: the oracle).  With ``dtype=np.float32`` and float32 parameters the
+same operations run in float32 throughout.  That run is no reference: it measures what float32 rounding alone costs
+at a given depth, and the GPU tests derive the tolerances of the deep shapes from it (``as_dtype`` casts a parameter
+list).
 """
 import numpy as np
 
 from oracle.bore_oracle import AdamState, _act, _act_grad_from_output, _sigmoid, _transform, adam_step, \
     bce_with_logits
 
-__all__ = ["unpack", "pack", "forward", "one_to_one", "loss_and_grads", "evaluate", "fit",
+__all__ = ["unpack", "pack", "as_dtype", "forward", "one_to_one", "loss_and_grads", "evaluate", "fit",
            "value_and_input_grad", "AdamState", "init_weights"]
 
 
@@ -47,6 +52,11 @@ def pack(params):
     return np.concatenate([np.asarray(p, dtype=np.float64).ravel() for p in params])
 
 
+def as_dtype(params, dtype):
+    """A copy of the parameter list in ``dtype``."""
+    return [np.array(p, dtype=dtype) for p in params]
+
+
 def init_weights(D, H, L, rs):
     """Random weights with the Keras initialisers' scales (tests only need plausible values)."""
     ps = []
@@ -70,16 +80,17 @@ def _live(X, mask_value):
     return np.any(X != mask_value, axis=-1)
 
 
-def forward(params, act, X, mask_value=None, cache=False):
-    """Many-to-many: X [n, T, D] -> logits [n, T] (mask_value None: no Masking layer)."""
-    X = np.asarray(X, dtype=np.float64)
+def forward(params, act, X, mask_value=None, cache=False, dtype=np.float64):
+    """Many-to-many: X [n, T, D] -> logits [n, T] (mask_value None: no Masking layer).  The cache keeps, per layer and
+    step, the gates, the candidate's pre-activation ``zg`` and the cell state ``c`` before the mask is applied."""
+    X = np.asarray(X, dtype=dtype)
     n, T, D = X.shape
     L = (len(params) - 2) // 3
     H = params[1].shape[0]
     live = _live(X, mask_value)
-    h = [np.zeros((n, H)) for _ in range(L)]
-    c = [np.zeros((n, H)) for _ in range(L)]
-    logits = np.zeros((n, T))
+    h = [np.zeros((n, H), dtype=dtype) for _ in range(L)]
+    c = [np.zeros((n, H), dtype=dtype) for _ in range(L)]
+    logits = np.zeros((n, T), dtype=dtype)
     C = [[None] * T for _ in range(L)]
     Wo, bo = params[-2], params[-1]
     with np.errstate(over="ignore", invalid="ignore"):
@@ -93,7 +104,7 @@ def forward(params, act, X, mask_value=None, cache=False):
                 g, o = _act(act, z[:, 2 * H:3 * H]), _sigmoid(z[:, 3 * H:])
                 cn = f * c[l] + i * g
                 hn = o * _act(act, cn)
-                C[l][t] = dict(inp=inp, hp=h[l], cp=c[l], i=i, f=f, g=g, o=o, c=cn)
+                C[l][t] = dict(inp=inp, hp=h[l], cp=c[l], i=i, f=f, g=g, o=o, c=cn, zg=z[:, 2 * H:3 * H])
                 c[l] = np.where(m, cn, c[l])
                 h[l] = np.where(m, hn, h[l])
                 C[l][t]["h"] = h[l]
@@ -104,15 +115,16 @@ def forward(params, act, X, mask_value=None, cache=False):
     return logits
 
 
-def one_to_one(params, act, x, num_steps):
+def one_to_one(params, act, x, num_steps, dtype=np.float64):
     """RepeatVector(num_steps) -> RNNs -> Dense: x [n, D] -> [n]."""
-    X = np.repeat(np.asarray(x, dtype=np.float64)[:, None, :], num_steps, axis=1)
-    return forward(params, act, X, None)[:, -1]
+    X = np.repeat(np.asarray(x, dtype=dtype)[:, None, :], num_steps, axis=1)
+    return forward(params, act, X, None, dtype=dtype)[:, -1]
 
 
 def backward(params, act, cache, dlogits):
-    """BPTT from d loss / d logits [n, T]: (grads in get_weights order, dx [n, T, D])."""
+    """BPTT from d loss / d logits [n, T]: (grads in get_weights order, dx [n, T, D]), in the dtype of dlogits."""
     C, live = cache
+    dt = dlogits.dtype
     L = (len(params) - 2) // 3
     T = len(C[0])
     H = params[1].shape[0]
@@ -122,10 +134,10 @@ def backward(params, act, cache, dlogits):
     for t in range(T):
         grads[-2][:, 0] += C[L - 1][t]["h"].T @ dlogits[:, t]
         grads[-1][0] += dlogits[:, t].sum()
-    dh = [np.zeros((n, H)) for _ in range(L)]
-    dc = [np.zeros((n, H)) for _ in range(L)]
+    dh = [np.zeros((n, H), dtype=dt) for _ in range(L)]
+    dc = [np.zeros((n, H), dtype=dt) for _ in range(L)]
     D = C[0][0]["inp"].shape[1]
-    dx = np.zeros((n, T, D))
+    dx = np.zeros((n, T, D), dtype=dt)
     for t in range(T - 1, -1, -1):
         above = dlogits[:, t][:, None] * Wo[:, 0][None, :]
         m = live[:, t][:, None]
@@ -138,7 +150,7 @@ def backward(params, act, cache, dlogits):
             dz = np.concatenate([dct * k["g"] * k["i"] * (1 - k["i"]), dct * k["cp"] * k["f"] * (1 - k["f"]),
                                  dct * k["i"] * _act_grad_from_output(act, k["g"]),
                                  dht * ac * k["o"] * (1 - k["o"])], axis=1)
-            dz = np.where(m, dz, 0.0)
+            dz = np.where(m, dz, dt.type(0))
             grads[3 * l] += k["inp"].T @ dz
             grads[3 * l + 1] += k["hp"].T @ dz
             grads[3 * l + 2] += dz.sum(axis=0)
@@ -159,64 +171,69 @@ def _penalty(params, l2k, l2b):
         iw, ib = (3 * l, 3 * l + 2) if l < L else (len(params) - 2, len(params) - 1)
         for idx, f in ((iw, fk), (ib, fb)):
             if f:
+                f = params[idx].dtype.type(f)
                 pen += f * np.sum(params[idx] ** 2)
                 g[idx] = 2 * f * params[idx]
     return pen, g
 
 
-def loss_and_grads(params, act, X, Y, mask_value, l2k=None, l2b=None):
-    logits, cache = forward(params, act, X, mask_value, cache=True)
+def loss_and_grads(params, act, X, Y, mask_value, l2k=None, l2b=None, dtype=np.float64):
+    logits, cache = forward(params, act, X, mask_value, cache=True, dtype=dtype)
     live = cache[1]
     n, T = logits.shape
-    Y = np.asarray(Y, dtype=np.float64).reshape(n, T)
+    Y = np.asarray(Y, dtype=dtype).reshape(n, T)
+    zero, nT = logits.dtype.type(0), logits.dtype.type(n * T)
     with np.errstate(over="ignore", invalid="ignore"):
-        el = np.where(live, bce_with_logits(logits, Y), 0.0)
-    loss = el.sum() / (n * T)
-    dlog = np.where(live, (_sigmoid(logits) - Y) / (n * T), 0.0)
+        el = np.where(live, bce_with_logits(logits, Y), zero)
+    loss = el.sum() / nT
+    dlog = np.where(live, (_sigmoid(logits) - Y) / nT, zero)
     grads, _ = backward(params, act, cache, dlog)
     pen, gp = _penalty(params, l2k, l2b)
     return loss + pen, [a + b for a, b in zip(grads, gp)]
 
 
-def evaluate(params, act, X, Y, mask_value, l2k=None, l2b=None):
-    logits = forward(params, act, X, mask_value)
-    live = _live(np.asarray(X, dtype=np.float64), mask_value)
+def evaluate(params, act, X, Y, mask_value, l2k=None, l2b=None, dtype=np.float64):
+    logits = forward(params, act, X, mask_value, dtype=dtype)
+    live = _live(np.asarray(X, dtype=dtype), mask_value)
     n, T = logits.shape
-    Y = np.asarray(Y, dtype=np.float64).reshape(n, T)
+    Y = np.asarray(Y, dtype=dtype).reshape(n, T)
     with np.errstate(over="ignore", invalid="ignore"):
-        el = np.where(live, bce_with_logits(logits, Y), 0.0)
+        el = np.where(live, bce_with_logits(logits, Y), logits.dtype.type(0))
     pen, _ = _penalty(params, l2k, l2b)
     acc = np.sum(live & ((logits > 0.5) == (Y > 0.5))) / max(np.sum(live), 1)
-    return float(el.sum() / (n * T) + pen), float(acc)
+    return float(el.sum() / logits.dtype.type(n * T) + pen), float(acc)
 
 
 def fit(params, act, st, X, Y, perms, batch_size, mask_value, l2k=None, l2b=None, lr=1e-3, beta1=0.9,
-        beta2=0.999, eps=1e-7):
-    """Keras fit over sequences with explicit permutations; in place; returns the logged losses."""
-    X = np.asarray(X, dtype=np.float64)
-    Y = np.asarray(Y, dtype=np.float64).reshape(X.shape[:2])
+        beta2=0.999, eps=1e-7, dtype=np.float64, on_batch=None):
+    """Keras fit over sequences with explicit permutations; in place; returns the logged losses.
+    ``on_batch(params, idx)`` is called before every Adam step (tests that guard their own inputs look there)."""
+    X = np.asarray(X, dtype=dtype)
+    Y = np.asarray(Y, dtype=dtype).reshape(X.shape[:2])
     N = X.shape[0]
     hist = []
     for perm in np.asarray(perms):
         tot = 0.0
         for s in range(0, N, batch_size):
             idx = perm[s:s + batch_size]
-            loss, grads = loss_and_grads(params, act, X[idx], Y[idx], mask_value, l2k, l2b)
+            if on_batch is not None:
+                on_batch(params, idx)
+            loss, grads = loss_and_grads(params, act, X[idx], Y[idx], mask_value, l2k, l2b, dtype)
             adam_step(params, grads, st, lr, beta1, beta2, eps)
             tot += float(loss) * len(idx)
         hist.append(tot / N)
     return np.asarray(hist)
 
 
-def value_and_input_grad(params, act, X, num_steps, transform="identity", negate=True):
+def value_and_input_grad(params, act, X, num_steps, transform="identity", negate=True, dtype=np.float64):
     """convert(one_to_one, transform) with negate: (T(+-f(x)) [R], d/dx [R, D]), summed over the steps."""
-    X = np.asarray(X, dtype=np.float64)
+    X = np.asarray(X, dtype=dtype)
     R = X.shape[0]
     Xs = np.repeat(X[:, None, :], num_steps, axis=1)
-    logits, cache = forward(params, act, Xs, None, cache=True)
-    s = -1.0 if negate else 1.0
+    logits, cache = forward(params, act, Xs, None, cache=True, dtype=dtype)
+    s = logits.dtype.type(-1.0 if negate else 1.0)
     val, dT = _transform(transform, s * logits[:, -1])
-    dlog = np.zeros((R, num_steps))
+    dlog = np.zeros((R, num_steps), dtype=dtype)
     dlog[:, -1] = s * dT
     _, dx = backward(params, act, cache, dlog)
     return val, dx.sum(axis=1)

@@ -137,6 +137,40 @@ def test_param_count_and_bad_descriptors(built):
     assert f.count_params() == 14625
 
 
+def test_reachable_lstm_bounds_are_the_lds_budget(built):
+    """The layout is decided before any pointer is looked at and before any HIP call, so bore_lstm_forward with null
+    data pointers reports that verdict alone: BORE_E_UNSUPPORTED with the LDS message for a network that does not fit
+    one workgroup's 160 KB, BORE_E_INVALID ("null pointer") for one that does."""
+    from bore_amd import _lib
+
+    def verdict(D, L, H, T):
+        d = _lib.make_lstm_desc(D, L, H, "elu")
+        rc = built.bore_lstm_forward(ctypes.byref(d), 1, None, None, 1, T, 0, 0.0, None, None)
+        return rc, built.bore_last_error().decode()
+
+    def fits(D, L, H, T):
+        rc, msg = verdict(D, L, H, T)
+        assert (rc == -1 and "null pointer" in msg) or (rc == -2 and "LDS" in msg), (rc, msg)
+        return rc == -1
+
+    # BORE_LSTM_MAX_UNITS is 64, but no network of 59 or more units fits: not at the smallest shape, hence at none
+    for H in range(59, 65):
+        rc, msg = verdict(1, 1, H, 1)
+        assert rc == -2 and "LDS" in msg and "%d units" % H in msg, (H, rc, msg)
+    assert fits(1, 1, 58, 1)
+    # one layer: 57 units at 2 inputs and one step, 54 at 16 steps
+    assert fits(2, 1, 57, 1) and not fits(2, 1, 58, 1)
+    assert fits(2, 1, 54, 16) and not fits(2, 1, 55, 16)
+    assert fits(2, 1, 56, 1) and "187408 B of LDS" in verdict(2, 1, 64, 1)[1]
+    # the plugin default, 2 x 32 units, at every D <= 16 and T <= 16 (151376 B of 163840 at 16 inputs and 16 steps)
+    for D in (1, 2, 16):
+        for T in (1, 5, 16):
+            assert fits(D, 2, 32, T), (D, T)
+    # a third layer of 32 units does not fit any more
+    rc, msg = verdict(2, 3, 32, 5)
+    assert rc == -2 and "182032 B of LDS" in msg, (rc, msg)
+
+
 def test_lstm_descriptor_layout_matches_the_header(tmp_path):
     if shutil.which("gcc") is None:
         pytest.skip("no gcc")
