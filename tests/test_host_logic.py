@@ -262,6 +262,11 @@ def test_tools_and_committed_measurements_are_readable():
         reps = line["configs"][cfg]["many_loops"]["ms_reps"]
         assert reps["n"] >= 5 and reps["min"]["lbfgsb"] <= line["configs"][cfg]["many_loops"]["ms"]["lbfgsb"] <= reps["max"]["lbfgsb"]
     assert line["unit"] == "BO-iterations/s" and line["roofline"]["frac"] > 0 and line["cpu_baseline"]["value"] > 0
+    # (the numeric-range suite: the float32 oracle's margins its tolerances read, and the ratios measured on the device)
+    margin = json.load(open(os.path.join(root, "profiles", "numeric_range", "oracle_margin.json")))
+    assert margin["adam_f32_ratio"] and margin["sensitivity"] and margin["dropped"] == []
+    measured = json.load(open(os.path.join(root, "profiles", "numeric_range", "parity_measured.json")))
+    assert {"numeric_range/fit_logit", "numeric_range/fit_hidden", "numeric_range/fit_adam", "numeric_range/lstm"} <= set(measured)
 
 
 def test_history_is_lazy_and_assignable_like_keras():
