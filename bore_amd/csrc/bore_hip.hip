@@ -2248,9 +2248,22 @@ __global__ __launch_bounds__(BORE_THREADS) void shuffle_kernel(unsigned long lon
 // ---------------------------------------------------------------------------
 // host side of the C-ABI
 // ---------------------------------------------------------------------------
-static int fit_bf16_impl(const bore_mlp_desc *, int, float *, float *, float *, int64_t *,
-                         const float *, const float *, int64_t, int, int, const int32_t *, uint64_t,
-                         int64_t, int64_t, const bore_adam_cfg *, float *, void *);
+// What bore_mlp_fit is asked for: its arguments up to `stream`, under their names in include/bore_hip.h.
+struct FitRequest {
+  const bore_mlp_desc *desc;
+  int n_models;
+  float *theta, *adam_m, *adam_v;
+  int64_t *adam_t;
+  const float *X, *z;
+  int64_t N;
+  int epochs, batch_size;
+  const int32_t *perm;
+  uint64_t seed;
+  int64_t model_index0, epoch0;
+  const bore_adam_cfg *adam;
+  float *epoch_loss;
+};
+static int fit_bf16_impl(const FitRequest &r, void *stream);
 
 // The streamed flavour (bore_stream.hip): float32 networks whose parameters stay in global memory.  An entry point
 // below goes there exactly when its own LDS check refuses the network for capacity, or when BORE_STREAM=1 asks.
@@ -2260,21 +2273,50 @@ static int stream_value_and_input_grad(const bore_mlp_desc *, int, const float *
                                        float *, double *, void *);
 static int stream_evaluate(const bore_mlp_desc *, int, const float *, const float *, const float *, int64_t, float *,
                            float *, void *);
-static int stream_fit(const bore_mlp_desc *, int, float *, float *, float *, int64_t *, const float *, const float *,
-                      int64_t, int, int, const int32_t *, uint64_t, int64_t, int64_t, const bore_adam_cfg *, float *,
-                      void *);
+static int stream_fit(const FitRequest &r, void *stream);
 static bool stream_takes(const bore_mlp_desc *desc, int rc) {
   return rc == BORE_E_UNSUPPORTED && desc && desc->compute == BORE_COMPUTE_F32 && !g_batch;
 }
 
-// Arguments, LDS bytes and kernel flavour of a float32 fit launch (what bore_mlp_fit launches;
-// the fused iteration kernel of bore_iter.hip builds its fit phase with it).  Returns 1 when
-// there is nothing to do (epochs == 0).
-static int fit_build(const bore_mlp_desc *desc, int n_models, float *theta, float *adam_m,
-                     float *adam_v, int64_t *adam_t, const float *X, const float *z, int64_t N,
-                     int epochs, int batch_size, const int32_t *perm, uint64_t seed,
-                     int64_t model_index0, int64_t epoch0, const bore_adam_cfg *adam,
-                     float *epoch_loss, FitArgs &a, size_t &lds_floats, int &shape_out) {
+// What a fit request has to be whichever flavour runs it (fit_build, stream_fit), over the network's layout: one
+// sigmoid or linear output unit, its pointers, epochs.  Returns 1 when there is nothing to do (epochs == 0).
+static int fit_check_request(const MlpLayout &L, const FitRequest &r) {
+  if (L.w[L.n_layers] != 1)
+    return fail(BORE_E_INVALID, "fit: the last Dense layer must have 1 unit (binary classifier)");
+  if (L.act[L.n_layers] != BORE_ACT_SIGMOID && L.act[L.n_layers] != BORE_ACT_LINEAR)
+    return fail(BORE_E_INVALID, "fit: BCE needs a sigmoid or linear (from_logits) output layer");
+  if (!r.theta || !r.adam_m || !r.adam_v || !r.adam_t || !r.X || !r.z || !r.adam)
+    return fail(BORE_E_INVALID, "fit: null pointer");
+  if (r.epochs < 0) return fail(BORE_E_INVALID, "fit: epochs < 0");
+  return r.epochs == 0;
+}
+
+// The request's fields that FitArgs, FitBf16Args and StreamFitArgs have in common (SEEDED = false: the streamed fit,
+// which is handed its shuffles ready-made).
+template <bool SEEDED = true, class A>
+static void fit_fill(A &a, const FitRequest &r) {
+  a.theta = r.theta; a.am = r.adam_m; a.av = r.adam_v; a.at = (long long *)r.adam_t;
+  a.X = r.X; a.z = r.z; a.perm = r.perm; a.epoch_loss = r.epoch_loss;
+  a.N = (int)r.N; a.epochs = r.epochs; a.B = r.batch_size;
+  a.lr = r.adam->lr; a.beta1 = r.adam->beta1; a.beta2 = r.adam->beta2; a.eps = r.adam->eps;
+  if constexpr (SEEDED) { a.seed = r.seed; a.model0 = r.model_index0; a.epoch0 = r.epoch0; }
+}
+
+// A float32 fit launch as planned from the request's sizes alone.
+struct FitPlan {
+  FitArgs a;  // fit_plan: the layout, the LDS carve and the *_in_lds / perm_ahead flags; fit_build: the rest
+  size_t lds_floats;
+  int flavour;
+  bool fits;  // the network and the shuffle have their place (a.L stands): a refusal after that is the carve's
+  bool w8;    // the flavour and the carve admit the eight-wave kernel (fit_wants_w8 has the launch's say)
+};
+
+// Capacity checks, LDS carve and kernel flavour of a float32 fit: no pointer of the request is looked at, `batch` is
+// the batch mode it runs in (bore_set_batch; nullptr: none).  bore_mlp_streamed and fit_padded ask it on its own.
+static int fit_plan(const bore_mlp_desc *desc, int n_models, int64_t N, int batch_size, bool perm,
+                    const bore_batch *batch, FitPlan &p) {
+  FitArgs &a = p.a;
+  p.fits = false;
   if (batch_size < 1) return fail(BORE_E_INVALID, "fit: batch_size must be positive (got %d)", batch_size);
   if (N < 1 || N > (1 << 24)) return fail(BORE_E_INVALID, "fit: N=%lld out of range", (long long)N);
   // a mini-batch of up to 64 rows is one tile (larger ones: 64-row sub-tiles, fit_body); perm
@@ -2282,37 +2324,32 @@ static int fit_build(const bore_mlp_desc *desc, int n_models, float *theta, floa
   const int tile_rows = batch_size < BORE_BATCH_MAX ? batch_size : BORE_BATCH_MAX;
   // (the parked-row slots of fit_body: the narrow static shapes only -- a wide one has no LDS to spare)
   // (the fit-only static shape: not in batch mode -- the fused iteration kernels have no case for it)
-  auto fit_flavour = [&](const bore_mlp_desc *d) {
-    return g_batch ? bore_kernel_flavour(d, batch_size == BORE_BATCH_MAX) : bore_fit_flavour(d, batch_size == BORE_BATCH_MAX);
-  };
-  const int flavour_early = desc ? fit_flavour(desc) : 0;
-  const size_t stage_f = flavour_early > 0 && !bore_shape_is_wide(flavour_early) ? BORE_FIT_STAGE_FLOATS_OF(flavour_early) : 0;
+  const int fl = !desc ? 0 : batch ? bore_kernel_flavour(desc, batch_size == BORE_BATCH_MAX)
+                                   : bore_fit_flavour(desc, batch_size == BORE_BATCH_MAX);
+  const size_t stage_f = fl > 0 && !bore_shape_is_wide(fl) ? BORE_FIT_STAGE_FLOATS_OF(fl) : 0;
   const size_t fixed_extra = BORE_BATCH_MAX + 8 + stage_f + BORE_LAYOUT_FLOATS + 12;
   // 32->128-128-1 in float32 with 64-row batches: theta and the 64-row images do not share the LDS;
   // the weight gradients are formed in four rounds over 16-row images instead (wide_rounds_f32)
-  const bool rounds = desc && desc->compute != BORE_COMPUTE_BF16 && batch_size == BORE_BATCH_MAX && !g_batch &&
+  const bool rounds = desc && desc->compute != BORE_COMPUTE_BF16 && batch_size == BORE_BATCH_MAX && !batch &&
                       bore_shape_fit_in_rounds(bore_kernel_flavour(desc, true));
-  int rc;
+  int rc = 0;
   if (rounds) {
     if (n_models < 1) return fail(BORE_E_INVALID, "n_models must be >= 1 (got %d)", n_models);
     if (bore_make_layout(desc, 1, BORE_BATCH_MAX, &a.L)) return fail(BORE_E_INVALID, "bad bore_mlp_desc");
     a.L.tile_floats = WideTp16<4>::total();  // (the kernel's images; the row-major tile is not used)
     const size_t need = (size_t)a.L.P_lds + a.L.tile_floats + fixed_extra + (size_t)N * (perm ? 1 : 3);
-    rc = need * 4 <= BORE_LDS_BYTES ? 0 : BORE_E_UNSUPPORTED;
-    if (rc) {
+    if (need * 4 > BORE_LDS_BYTES) {
       const size_t avail = BORE_LDS_BYTES / 4 - ((size_t)a.L.P_lds + a.L.tile_floats + fixed_extra);
       return fail(BORE_E_UNSUPPORTED,
                   "fit: N=%lld rows exceed what one workgroup's LDS holds beside this network (the "
                   "epoch's shuffle lives there): at most %zu rows",
                   (long long)N, avail / (perm ? 1 : 3));
     }
-  } else
-  rc = check_common(desc, n_models, 1, tile_rows, false, fixed_extra + (size_t)N * (perm ? 1 : 3),
-                    &a.L);
+  } else rc = check_common(desc, n_models, 1, tile_rows, false, fixed_extra + (size_t)N * (perm ? 1 : 3), &a.L);
   a.perm_in_lds = 1;
   if (rc == BORE_E_UNSUPPORTED && !check_common(desc, n_models, 1, tile_rows, false, fixed_extra, &a.L)) {
     // the network fits, the epoch's shuffle (drawn and ranked in LDS) does not
-    if (perm && !g_batch) {
+    if (perm && !batch) {
       // an EXPLICIT permutation of any length is read from memory step by step (round 3: the
       // reference's fit takes whatever the record holds; bore_amd.models draws such shuffles with
       // the host statement of the stream and passes them here)
@@ -2320,7 +2357,7 @@ static int fit_build(const bore_mlp_desc *desc, int n_models, float *theta, floa
       rc = 0;
     } else {
       const size_t avail = BORE_LDS_BYTES / 4 - ((size_t)a.L.P_lds + a.L.tile_floats + fixed_extra);
-      return fail(g_batch ? BORE_E_UNSUPPORTED : BORE_E_NEEDS_PERM,
+      return fail(batch ? BORE_E_UNSUPPORTED : BORE_E_NEEDS_PERM,
                   "fit: N=%lld rows exceed what one workgroup's LDS holds beside this network when the "
                   "epoch's shuffle is drawn on the device (at most %zu rows): pass explicit shuffles "
                   "(`perm`, e.g. from bore_amd.shuffle.permutations) -- any N then",
@@ -2328,30 +2365,11 @@ static int fit_build(const bore_mlp_desc *desc, int n_models, float *theta, floa
     }
   }
   if (rc) return rc;
+  p.fits = true;
   const MlpLayout &L = a.L;
-  if (L.w[L.n_layers] != 1)
-    return fail(BORE_E_INVALID, "fit: the last Dense layer must have 1 unit (binary classifier)");
-  if (L.act[L.n_layers] != BORE_ACT_SIGMOID && L.act[L.n_layers] != BORE_ACT_LINEAR)
-    return fail(BORE_E_INVALID, "fit: BCE needs a sigmoid or linear (from_logits) output layer");
-  if (!theta || !adam_m || !adam_v || !adam_t || !X || !z || !adam)
-    return fail(BORE_E_INVALID, "fit: null pointer");
-  if (epochs < 0) return fail(BORE_E_INVALID, "fit: epochs < 0");
-  if (epochs == 0) return 1;
-
-  a.theta = theta; a.am = adam_m; a.av = adam_v; a.at = (long long *)adam_t;
-  a.X = X; a.z = z; a.perm = perm; a.epoch_loss = epoch_loss;
-  a.seed = seed; a.model0 = model_index0; a.epoch0 = epoch0;
-  a.N = (int)N; a.epochs = epochs; a.B = batch_size;
-  a.lr = adam->lr; a.beta1 = adam->beta1; a.beta2 = adam->beta2; a.eps = adam->eps;
-  a.ids = a.its = nullptr; a.n_init = 0; a.cap = 0;
-  if (g_batch) {
-    if (perm || epoch_loss) return fail(BORE_E_INVALID, "fit: no perm / epoch_loss in batch mode");
-    a.ids = g_batch->ids; a.its = g_batch->its; a.n_init = g_batch->n_init; a.cap = g_batch->cap;
-  }
 
   // LDS carve: theta | tile | zt | misc | stage | perm | keys | [m v] | [X z]
-  size_t off = 0;
-  off += L.P_lds;
+  size_t off = L.P_lds;
   a.o_tile = (int)off; off += L.tile_floats;
   a.o_zt = (int)off; off += BORE_BATCH_MAX;
   a.o_misc = (int)off; off += 8;
@@ -2364,14 +2382,13 @@ static int fit_build(const bore_mlp_desc *desc, int n_models, float *theta, floa
   if (!perm && stage_f && keys_f < BORE_PERM_WAVE_FLOATS) keys_f = BORE_PERM_WAVE_FLOATS;
   a.perm_ahead = 0;  // (decided below, once everything else has its place)
   a.o_perm2 = 0;
-  if (g_batch)  // a slot's own N (<= this N) may shuffle more epochs together: room for each case
+  if (batch)  // a slot's own N (<= this N) may shuffle more epochs together: room for each case
     for (long long nn : {(long long)(N < 64 ? N : 64), (long long)(N < 128 ? N : 128)}) {
       const int pg = perm_group(nn, BORE_THREADS);
       if ((size_t)pg * nn > perm_f) perm_f = (size_t)pg * nn;
-      if ((size_t)perm_group_scratch_floats(nn, pg) > keys_f)
-        keys_f = (size_t)perm_group_scratch_floats(nn, pg);
+      if ((size_t)perm_group_scratch_floats(nn, pg) > keys_f) keys_f = (size_t)perm_group_scratch_floats(nn, pg);
     }
-  if (g_batch && stage_f) {  // (a slot of up to 128 rows in pipelined form: four shuffles)
+  if (batch && stage_f) {  // (a slot of up to 128 rows in pipelined form: four shuffles)
     const size_t nn = N < 128 ? (size_t)N : 128;
     if (perm_f < 4 * nn) perm_f = 4 * nn;
   }
@@ -2381,8 +2398,7 @@ static int fit_build(const bore_mlp_desc *desc, int n_models, float *theta, floa
   a.o_g = (int)off;
   if (batch_size > BORE_BATCH_MAX) off += L.P_lds;  // gradient sums carried between sub-tiles
   if ((off + BORE_LAYOUT_FLOATS + 4) * 4 > BORE_LDS_BYTES)
-    return fail(BORE_E_UNSUPPORTED, "fit: theta+tile+perm need %zu B of LDS (> %d)", off * 4,
-                BORE_LDS_BYTES);
+    return fail(BORE_E_UNSUPPORTED, "fit: theta+tile+perm need %zu B of LDS (> %d)", off * 4, BORE_LDS_BYTES);
   const size_t tail = BORE_LAYOUT_FLOATS + 4;  // the layout copy parked behind everything
   a.state_in_lds = (off + tail + 2 * (size_t)L.P_lds) * 4 <= BORE_LDS_BYTES;
   a.o_m = a.o_v = 0;
@@ -2397,23 +2413,19 @@ static int fit_build(const bore_mlp_desc *desc, int n_models, float *theta, floa
     a.o_X = (int)off; off += (size_t)N * L.w[0];
     a.o_z = (int)off; off += N;
   }
-  {  // 129..512 rows and a flavour with an eight-wave kernel: a second shuffle buffer (fit_body `ahead`) -- behind
-     // everything else and only when it still fits, so that it moves nothing and decides nothing
-    const int fl = fit_flavour(desc);
-    if (!perm && !g_batch && a.perm_in_lds && PG == 1 && N <= 512 && batch_size <= BORE_BATCH_MAX &&
-        (fl == 2 || fl == 5 || fl == BORE_FIT_SHAPE_16_32 || (fl < 0 && fl >= -4)) &&
-        (off + (size_t)N + tail) * 4 <= BORE_LDS_BYTES) {
-      a.perm_ahead = 1;
-      a.o_perm2 = (int)off; off += (size_t)N;
-    }
+  // 129..512 rows and a flavour with an eight-wave kernel: a second shuffle buffer (fit_body `ahead`) -- behind
+  // everything else and only when it still fits, so that it moves nothing and decides nothing
+  if (!perm && !batch && a.perm_in_lds && PG == 1 && N <= 512 && batch_size <= BORE_BATCH_MAX &&
+      bore_flavour_listed(FitW8Flavours{}, fl) && (off + (size_t)N + tail) * 4 <= BORE_LDS_BYTES) {
+    a.perm_ahead = 1;
+    a.o_perm2 = (int)off; off += (size_t)N;
   }
   a.total = (int)off;
   off = (off + 3) & ~(size_t)3;
   a.o_layout = (int)off;
-  const size_t off_layout = off;
   // the constexpr-layout instantiation needs the layout it was compiled for (64-row tile)
   // (and keeps the Adam slots in LDS unconditionally)
-  int shape = fit_flavour(desc);
+  int shape = fl;
   if (!a.perm_in_lds && shape > 0) {  // (only the generic flavours read the permutation from memory)
     if (bore_shape_is_wide(shape))
       return fail(BORE_E_UNSUPPORTED, "fit: N=%lld rows with this wide network: the shuffle must fit in LDS", (long long)N);
@@ -2429,8 +2441,32 @@ static int fit_build(const bore_mlp_desc *desc, int n_models, float *theta, floa
   }
   // (the LDS copy of the layout tables is the generic flavour's alone, begin_kernel: the others read a constant
   // expression or the kernel arguments -- 496 B that decide whether three loops of the fused kernel share a CU)
-  lds_floats = off_layout + (shape == 0 ? BORE_LAYOUT_FLOATS : 0);
-  shape_out = shape;
+  p.lds_floats = off + (shape == 0 ? BORE_LAYOUT_FLOATS : 0);
+  p.flavour = shape;
+  // Eight waves (fit_kernel_w8): a static flavour that has the kernel, and any net of up to four layers with more than
+  // four weight-gradient tiles whose Adam slots are in LDS
+  int tiles = 0;
+  for (int l = 1; l <= L.n_layers; ++l) tiles += (L.Np[l - 1] >> 4) * (L.Np[l] >> 4);
+  p.w8 = !batch && bore_flavour_listed(FitW8Flavours{}, shape) && (shape > 0 || (a.state_in_lds && tiles > 4));
+  return 0;
+}
+
+// Eight waves for a launch whose plan admits them: no more models than CUs, or as BORE_FIT_W8 = 0 / 1 forces (-1: unset).
+static bool fit_wants_w8(int n_models, int forced, int cus) { return forced < 0 ? n_models <= cus : forced != 0; }
+
+// The launch of a float32 fit request (bore_mlp_fit's; the fit phase of bore_iter.hip's fused kernel): the plan, the
+// request's own checks, its fields.  The request's faults are reported before a carve that does not fit -- the plan's
+// message stands when there are none.  Returns 1 when there is nothing to do (epochs == 0).
+static int fit_build(const FitRequest &r, FitPlan &p) {
+  const int planned = fit_plan(r.desc, r.n_models, r.N, r.batch_size, r.perm != nullptr, g_batch, p);
+  if (planned && !p.fits) return planned;
+  if (const int rc = fit_check_request(p.a.L, r)) return rc;
+  if (g_batch && (r.perm || r.epoch_loss)) return fail(BORE_E_INVALID, "fit: no perm / epoch_loss in batch mode");
+  if (planned) return planned;
+  FitArgs &a = p.a;
+  fit_fill(a, r);
+  a.ids = a.its = nullptr; a.n_init = 0; a.cap = 0;
+  if (g_batch) { a.ids = g_batch->ids; a.its = g_batch->its; a.n_init = g_batch->n_init; a.cap = g_batch->cap; }
   return 0;
 }
 
@@ -2453,21 +2489,20 @@ static int bore_pads_to_shape(const bore_mlp_desc *d) {
 // stream-ordered scratch (W_1 is the packed vector's first block, row-major [in][out]: the padded vector is the
 // same prefix, a gap of zeros, the same suffix), the static fit, the way back.  rc < 0 with nothing launched when
 // the padded shape's fit cannot take the request (the caller then runs the generic flavour).
-static int fit_padded(const bore_mlp_desc *desc, int S, int n_models, float *theta, float *adam_m, float *adam_v,
-                      int64_t *adam_t, const float *X, const float *z, int64_t N, int epochs, int batch_size,
-                      const int32_t *perm, uint64_t seed, int64_t model_index0, int64_t epoch0,
-                      const bore_adam_cfg *adam, float *epoch_loss, void *stream) {
+static int fit_run(const FitRequest &r, void *stream);
+static int fit_padded(const FitRequest &r, int S, void *stream) {
+  const bore_mlp_desc *desc = r.desc;
+  const int n_models = r.n_models;
+  const int64_t N = r.N;
   bore_mlp_desc dp = *desc;
   dp.input_dim = kShapes[S].D;
   const size_t D = desc->input_dim, DS = dp.input_dim, H = desc->units[0];
   const int64_t P = bore_param_count(desc), PS = bore_param_count(&dp);
-  {  // (would the static fit take it?  the same checks, nothing launched)
-    FitArgs probe;
-    size_t off = 0;
-    int shape = 0;
-    const int rc = fit_build(&dp, n_models, theta, adam_m, adam_v, adam_t, X, z, N, epochs, batch_size, perm, seed,
-                             model_index0, epoch0, adam, epoch_loss, probe, off, shape);
-    if (rc != 0 || shape != S) return BORE_E_UNSUPPORTED;
+  {  // (would the static fit take it?  its plan and the request's checks, nothing launched)
+    FitPlan p;
+    if (fit_plan(&dp, n_models, N, r.batch_size, r.perm != nullptr, g_batch, p) || p.flavour != S ||
+        fit_check_request(p.a.L, r))
+      return BORE_E_UNSUPPORTED;
   }
   hipStream_t st = (hipStream_t)stream;
   const size_t n_par = (size_t)n_models * PS, n_x = (size_t)n_models * N * DS;
@@ -2481,21 +2516,22 @@ static int fit_padded(const bore_mlp_desc *desc, int S, int n_models, float *the
                             hipMemcpyDeviceToDevice, st);
   };
   hipError_t e = hipMemsetAsync(buf, 0, (3 * n_par + n_x) * sizeof(float), st);
-  const float *user[3] = {theta, adam_m, adam_v};
+  float *user[3] = {r.theta, r.adam_m, r.adam_v};
   float *padded[3] = {th_p, m_p, v_p};
   for (int k = 0; k < 3 && e == hipSuccess; ++k) {
     e = copy_rows(padded[k], PS * 4, 0, user[k], P * 4, 0, head, n_models);
     if (e == hipSuccess) e = copy_rows(padded[k], PS * 4, DS * H * 4, user[k], P * 4, head, tail, n_models);
   }
-  if (e == hipSuccess) e = copy_rows(X_p, DS * 4, 0, X, D * 4, 0, D * 4, (size_t)n_models * N);
+  if (e == hipSuccess) e = copy_rows(X_p, DS * 4, 0, r.X, D * 4, 0, D * 4, (size_t)n_models * N);
   int rc = e == hipSuccess ? 0 : fail(BORE_E_HIP, "fit (padded to a static shape): %s", hipGetErrorString(e));
-  if (rc == 0)
-    rc = bore_mlp_fit(&dp, n_models, th_p, m_p, v_p, adam_t, X_p, z, N, epochs, batch_size, perm, seed, model_index0,
-                      epoch0, adam, epoch_loss, stream);
-  float *back[3] = {theta, adam_m, adam_v};
+  if (rc == 0) {
+    FitRequest rp = r;
+    rp.desc = &dp; rp.theta = th_p; rp.adam_m = m_p; rp.adam_v = v_p; rp.X = X_p;
+    rc = fit_run(rp, stream);
+  }
   for (int k = 0; k < 3 && rc == 0; ++k) {
-    e = copy_rows(back[k], P * 4, 0, padded[k], PS * 4, 0, head, n_models);
-    if (e == hipSuccess) e = copy_rows(back[k], P * 4, head, padded[k], PS * 4, DS * H * 4, tail, n_models);
+    e = copy_rows(user[k], P * 4, 0, padded[k], PS * 4, 0, head, n_models);
+    if (e == hipSuccess) e = copy_rows(user[k], P * 4, head, padded[k], PS * 4, DS * H * 4, tail, n_models);
     if (e != hipSuccess) rc = fail(BORE_E_HIP, "fit (padded to a static shape): %s", hipGetErrorString(e));
   }
   (void)hipFreeAsync(buf, st);
@@ -2507,113 +2543,93 @@ extern "C" int bore_mlp_fit(const bore_mlp_desc *desc, int n_models, float *thet
                             int64_t N, int epochs, int batch_size, const int32_t *perm,
                             uint64_t seed, int64_t model_index0, int64_t epoch0,
                             const bore_adam_cfg *adam, float *epoch_loss, void *stream) {
+  return fit_run(FitRequest{desc, n_models, theta, adam_m, adam_v, adam_t, X, z, N, epochs, batch_size, perm, seed,
+                            model_index0, epoch0, adam, epoch_loss},
+                 stream);
+}
+
+static int fit_run(const FitRequest &r, void *stream) {
+  const bore_mlp_desc *desc = r.desc;
+  const int n_models = r.n_models;
   // (BORE_STREAM = 1: in front of everything, the zero-padded detour included)
-  if (stream_forced(desc))
-    return stream_fit(desc, n_models, theta, adam_m, adam_v, adam_t, X, z, N, epochs, batch_size, perm, seed,
-                      model_index0, epoch0, adam, epoch_loss, stream);
+  if (stream_forced(desc)) return stream_fit(r, stream);
   // (BORE_FIT_PAD = 0: such nets on the generic flavour, as before round 4 -- A/B, tests)
-  if (desc && !g_batch && theta && adam_m && adam_v && adam_t && X && z && adam && epochs > 0 && n_models >= 1 &&
-      N >= 1 && batch_size == BORE_BATCH_MAX && !(getenv("BORE_FIT_PAD") && !atoi(getenv("BORE_FIT_PAD")))) {
+  // (fit_padded leaves a request with a fault of its own, or with nothing to do, to the checks below)
+  if (desc && !g_batch && r.batch_size == BORE_BATCH_MAX && !(getenv("BORE_FIT_PAD") && !atoi(getenv("BORE_FIT_PAD")))) {
     const int S = bore_pads_to_shape(desc);
     if (S) {
-      const int rc = fit_padded(desc, S, n_models, theta, adam_m, adam_v, adam_t, X, z, N, epochs, batch_size, perm,
-                                seed, model_index0, epoch0, adam, epoch_loss, stream);
+      const int rc = fit_padded(r, S, stream);
       if (rc != BORE_E_UNSUPPORTED) return rc;
     }
   }
   if (desc && desc->compute == BORE_COMPUTE_BF16) {
     if (g_batch) return fail(BORE_E_UNSUPPORTED, "fit: batch mode is float32 only");
-    return fit_bf16_impl(desc, n_models, theta, adam_m, adam_v, adam_t, X, z, N, epochs, batch_size,
-                         perm, seed, model_index0, epoch0, adam, epoch_loss, stream);
+    return fit_bf16_impl(r, stream);
   }
-  FitArgs a;
-  size_t off = 0;
-  int shape = 0;
-  int rc = fit_build(desc, n_models, theta, adam_m, adam_v, adam_t, X, z, N, epochs, batch_size, perm,
-                     seed, model_index0, epoch0, adam, epoch_loss, a, off, shape);
-  if (stream_takes(desc, rc))  // (refused for capacity: the streamed flavour, or its own bound by name)
-    return stream_fit(desc, n_models, theta, adam_m, adam_v, adam_t, X, z, N, epochs, batch_size, perm, seed,
-                      model_index0, epoch0, adam, epoch_loss, stream);
+  FitPlan p;
+  const int rc = fit_build(r, p);
+  // (refused for capacity: the streamed flavour, or its own bound by name)
+  if (stream_takes(desc, rc)) return stream_fit(r, stream);
   if (rc) return rc < 0 ? rc : 0;
-  {  // Eight waves (fit_kernel_w8): 6->32-32-1, and any net of up to four layers with more than four weight-gradient
-     // tiles whose Adam slots are in LDS -- launches with no more models than CUs.  BORE_FIT_W8 = 0 / 1 forces the
-     // choice (A/B, tests).
-    const int forced = getenv("BORE_FIT_W8") ? atoi(getenv("BORE_FIT_W8")) : -1;
-    int tiles = 0;
-    for (int l = 1; l <= a.L.n_layers; ++l) tiles += (a.L.Np[l - 1] >> 4) * (a.L.Np[l] >> 4);
-    const bool can = !g_batch && (shape == 2 || shape == 5 || shape == BORE_FIT_SHAPE_16_32 ||
-                                  (shape < 0 && shape >= -4 && a.state_in_lds && tiles > 4));
-    if (can && (forced < 0 ? n_models <= device_cus() : forced != 0))
-      return bore_with_flavour(FitW8Flavours{}, shape, [&](auto S) {
-        return launch_lds(fit_kernel_w8<S()>, dim3(n_models), dim3(2 * BORE_THREADS), off * 4, stream, a);
-      });
-  }
-  return bore_with_flavour(FitFlavours{}, shape, [&](auto S) {
-    return launch_lds(fit_kernel<S()>, dim3(n_models), dim3(BORE_THREADS), off * 4, stream, a);
+  const int forced = getenv("BORE_FIT_W8") ? atoi(getenv("BORE_FIT_W8")) : -1;
+  if (p.w8 && fit_wants_w8(n_models, forced, device_cus()))
+    return bore_with_flavour(FitW8Flavours{}, p.flavour, [&](auto S) {
+      return launch_lds(fit_kernel_w8<S()>, dim3(n_models), dim3(2 * BORE_THREADS), p.lds_floats * 4, stream, p.a);
+    });
+  return bore_with_flavour(FitFlavours{}, p.flavour, [&](auto S) {
+    return launch_lds(fit_kernel<S()>, dim3(n_models), dim3(BORE_THREADS), p.lds_floats * 4, stream, p.a);
   });
 }
 
-static int fit_bf16_impl(const bore_mlp_desc *desc, int n_models, float *theta, float *adam_m,
-                         float *adam_v, int64_t *adam_t, const float *X, const float *z, int64_t N,
-                         int epochs, int batch_size, const int32_t *perm, uint64_t seed,
-                         int64_t model_index0, int64_t epoch0, const bore_adam_cfg *adam,
-                         float *epoch_loss, void *stream) {
+static int fit_bf16_impl(const FitRequest &r, void *stream) {
   FitBf16Args a;
-  if (batch_size != BORE_BATCH_MAX)
-    return fail(BORE_E_UNSUPPORTED, "fit_bf16: batch_size must be %d (got %d)", BORE_BATCH_MAX,
-                batch_size);
+  const int64_t N = r.N;
+  if (r.batch_size != BORE_BATCH_MAX)
+    return fail(BORE_E_UNSUPPORTED, "fit_bf16: batch_size must be %d (got %d)", BORE_BATCH_MAX, r.batch_size);
   if (N < 1 || N > (1 << 20)) return fail(BORE_E_INVALID, "fit_bf16: N=%lld out of range", (long long)N);
-  if (epochs < 0) return fail(BORE_E_INVALID, "fit_bf16: epochs < 0");
-  if (n_models < 1) return fail(BORE_E_INVALID, "n_models must be >= 1 (got %d)", n_models);
-  if (!desc || !theta || !adam_m || !adam_v || !adam_t || !X || !z || !adam)
+  if (r.epochs < 0) return fail(BORE_E_INVALID, "fit_bf16: epochs < 0");
+  if (r.n_models < 1) return fail(BORE_E_INVALID, "n_models must be >= 1 (got %d)", r.n_models);
+  if (!r.desc || !r.theta || !r.adam_m || !r.adam_v || !r.adam_t || !r.X || !r.z || !r.adam)
     return fail(BORE_E_INVALID, "fit_bf16: null pointer");
-  const int shape = bore_match_shape(desc);
-  if (!bore_shape_is_wide(shape))
-    return fail(BORE_E_UNSUPPORTED, kBf16Shapes);
-  if (bore_make_layout(desc, 1, BORE_BATCH_MAX, &a.L)) return fail(BORE_E_INVALID, "bad bore_mlp_desc");
-  if (epochs == 0) return 0;
-  a.theta = theta; a.am = adam_m; a.av = adam_v; a.at = (long long *)adam_t;
-  a.X = X; a.z = z; a.perm = perm; a.epoch_loss = epoch_loss;
-  a.seed = seed; a.model0 = model_index0; a.epoch0 = epoch0;
-  a.N = (int)N; a.epochs = epochs; a.B = batch_size;
-  a.lr = adam->lr; a.beta1 = adam->beta1; a.beta2 = adam->beta2; a.eps = adam->eps;
-  // The bf16-MFMA kernel keeps two fragment-order weight images in LDS; with a long shuffle
-  // (perm + keys grow with N) it no longer fits beside them and the fp32-MFMA form takes over.
-  const int PGn = perm ? 1 : perm_group(N, BORE_THREADS);
-  const size_t perm_bytes = 4 * (size_t)PGn * N + (perm ? 0 : 4 * (size_t)perm_group_scratch_floats(N, PGn)) + 96;
-  const size_t new_bytes = (shape == 3 ? Bf16Plan<3>::o_end : Bf16Plan<4>::o_end) + perm_bytes;
-  const bool old_form = new_bytes > BORE_LDS_BYTES;
+  const int shape = bore_match_shape(r.desc);
+  if (!bore_shape_is_wide(shape)) return fail(BORE_E_UNSUPPORTED, kBf16Shapes);
+  if (bore_make_layout(r.desc, 1, BORE_BATCH_MAX, &a.L)) return fail(BORE_E_INVALID, "bad bore_mlp_desc");
+  if (r.epochs == 0) return 0;
+  fit_fill(a, r);
+  // the shuffle: perm (the epochs drawn together), and the keys it is ranked by when the device draws it
+  const int PG = r.perm ? 1 : perm_group(N, BORE_THREADS);
+  const size_t perm_bytes = 4 * (size_t)PG * N;
+  const size_t keys_bytes = r.perm ? 0 : 4 * (size_t)perm_group_scratch_floats(N, PG);
+  // The bf16-MFMA kernel keeps two fragment-order weight images in LDS; with a long shuffle it no longer fits beside
+  // them and the fp32-MFMA form takes over.  (96: the 32 bytes of misc and more than the alignments below can add)
+  const size_t images = shape == 3 ? Bf16Plan<3>::o_end : Bf16Plan<4>::o_end;
+  static_assert(Bf16Plan<3>::fits() && Bf16Plan<4>::fits(), "a layer's gradients must fit the image region");
+  const bool old_form = images + perm_bytes + keys_bytes + 96 > BORE_LDS_BYTES;
   // LDS carve (bytes).  bf16-MFMA form: weight images | biases | A^T / D^T images (= gradient
   // image) | misc | perm | keys;  fp32-MFMA form: theta bf16 | A/D copies bf16 | misc | perm | keys
-  size_t off;
+  size_t off = images;
+  a.o_tile = 0;
   if (old_form) {
-    off = 2 * (size_t)a.L.P_lds;
-    off = (off + 15) & ~(size_t)15;
+    off = (2 * (size_t)a.L.P_lds + 15) & ~(size_t)15;
     // (the weight-gradient phase parks the packed fp32 gradient image over the A / D copies)
     a.o_tile = (int)off;
     off += 2 * (size_t)a.L.tile_floats > 4 * (size_t)a.L.P ? 2 * (size_t)a.L.tile_floats : 4 * (size_t)a.L.P;
-  } else {
-    a.o_tile = 0;
-    off = shape == 3 ? Bf16Plan<3>::o_end : Bf16Plan<4>::o_end;
-    static_assert(Bf16Plan<3>::fits() && Bf16Plan<4>::fits(), "a layer's gradients must fit the image region");
   }
   off = (off + 15) & ~(size_t)15;
   a.o_misc = (int)off; off += 8 * 4;
-  const int PG = perm ? 1 : perm_group(N, BORE_THREADS);
-  a.o_perm = (int)off; off += 4 * (size_t)PG * N;
+  a.o_perm = (int)off; off += perm_bytes;
   off = (off + 15) & ~(size_t)15;
-  a.o_keys = (int)off; off += perm ? 0 : 4 * (size_t)perm_group_scratch_floats(N, PG);
+  a.o_keys = (int)off; off += keys_bytes;
   off = (off + 15) & ~(size_t)15;
   a.total = (int)off;
   if (off > BORE_LDS_BYTES)
-    return fail(BORE_E_UNSUPPORTED, "fit_bf16: weights+images+perm need %zu B of LDS (> %d)", off,
-                BORE_LDS_BYTES);
+    return fail(BORE_E_UNSUPPORTED, "fit_bf16: weights+images+perm need %zu B of LDS (> %d)", off, BORE_LDS_BYTES);
   if (old_form)
     return bore_with_flavour(WideFlavours{}, shape, [&](auto S) {
-      return launch_lds(fit_bf16_kernel<S()>, dim3(n_models), dim3(BORE_THREADS), off, stream, a);
+      return launch_lds(fit_bf16_kernel<S()>, dim3(r.n_models), dim3(BORE_THREADS), off, stream, a);
     });
   return bore_with_flavour(WideFlavours{}, shape, [&](auto S) {
-    return launch_lds(fit_bf16_mfma_kernel<S()>, dim3(n_models), dim3(BORE_THREADS), off, stream, a);
+    return launch_lds(fit_bf16_mfma_kernel<S()>, dim3(r.n_models), dim3(BORE_THREADS), off, stream, a);
   });
 }
 

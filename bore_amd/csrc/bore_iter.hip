@@ -487,11 +487,16 @@ struct IterPlan {
 static int iteration_plan(const IterEngine &E, const Worker &w, int n_slots, IterArgs *h, IterPlan *plan) {
   if (!g_batch) return fail(BORE_E_INVALID, "iteration_launch: no batch set");
   const int64_t cap = g_batch->cap;
-  size_t lf = 0, ls = 0, lb = 0;
-  int sf = 0, ss = 0, sb = 0, blocks = 0;
-  int rc = fit_build(E.desc, n_slots, E.theta, E.adam_m, E.adam_v, E.adam_t, E.X32, E.z, cap, E.epochs, E.batch_size,
-                     nullptr, E.seed, E.loop_id0, 0, E.adam, nullptr, h->f, lf, sf);
+  size_t ls = 0, lb = 0;
+  int ss = 0, sb = 0, blocks = 0;
+  FitPlan fit;
+  int rc = fit_build(FitRequest{E.desc, n_slots, E.theta, E.adam_m, E.adam_v, E.adam_t, E.X32, E.z, cap, E.epochs,
+                                E.batch_size, nullptr, E.seed, E.loop_id0, 0, E.adam, nullptr},
+                     fit);
   if (rc) return rc < 0 ? rc : fail(BORE_E_INVALID, "iteration_launch: epochs must be positive");
+  h->f = fit.a;
+  const size_t lf = fit.lds_floats;
+  const int sf = fit.flavour;
   const SampleSpec spec{E.seed, E.loop_id0, 0, E.low, E.high};
   if ((rc = screen_build(E.desc, n_slots, E.theta, nullptr, &spec, E.num_samples, 0, E.num_starts, w.x0, w.idx,
                          nullptr, h->s, ls, ss)))

@@ -846,39 +846,29 @@ static int stream_evaluate(const bore_mlp_desc *desc, int n_models, const float 
   return 0;
 }
 
-static int stream_fit(const bore_mlp_desc *desc, int n_models, float *theta, float *adam_m, float *adam_v,
-                      int64_t *adam_t, const float *X, const float *z, int64_t N, int epochs, int batch_size,
-                      const int32_t *perm, uint64_t seed, int64_t model_index0, int64_t epoch0,
-                      const bore_adam_cfg *adam, float *epoch_loss, void *stream) {
+static int stream_fit(const FitRequest &r, void *stream) {
   StreamFitArgs a;
-  if (const int rc = stream_bounds(desc, &a.L)) return rc;
+  const int n_models = r.n_models, epochs = r.epochs, batch_size = r.batch_size;
+  const int64_t N = r.N;
+  if (const int rc = stream_bounds(r.desc, &a.L)) return rc;
   if (n_models < 1) return fail(BORE_E_INVALID, "n_models must be >= 1 (got %d)", n_models);
   if (batch_size < 1) return fail(BORE_E_INVALID, "fit: batch_size must be positive (got %d)", batch_size);
   if (N < 1 || N > (1 << 24)) return fail(BORE_E_INVALID, "fit: N=%lld out of range", (long long)N);
   const MlpLayout &L = a.L;
-  if (L.w[L.n_layers] != 1)
-    return fail(BORE_E_INVALID, "fit: the last Dense layer must have 1 unit (binary classifier)");
-  if (L.act[L.n_layers] != BORE_ACT_SIGMOID && L.act[L.n_layers] != BORE_ACT_LINEAR)
-    return fail(BORE_E_INVALID, "fit: BCE needs a sigmoid or linear (from_logits) output layer");
-  if (!theta || !adam_m || !adam_v || !adam_t || !X || !z || !adam) return fail(BORE_E_INVALID, "fit: null pointer");
-  if (epochs < 0) return fail(BORE_E_INVALID, "fit: epochs < 0");
-  if (epochs == 0) return 0;
+  if (const int rc = fit_check_request(L, r)) return rc < 0 ? rc : 0;
   // the call's shuffles, when the caller passes none: the project's one stream (shuffle_kernel), drawn into the
   // scratch in front of the fit on the same stream
-  const size_t perm_ints = perm ? 0 : (size_t)n_models * epochs * N;
+  const size_t perm_ints = r.perm ? 0 : (size_t)n_models * epochs * N;
   // (as long as shuffle_kernel can rank N rows in LDS and the call's shuffles take no more than STREAM_WS_BYTES;
   // beyond: the caller's turn, which bore_amd.models takes a few epochs per launch)
-  if (!perm && (epochs > 65535 || (size_t)perm_scratch_floats(N) * 4 > BORE_LDS_BYTES ||
+  if (!r.perm && (epochs > 65535 || (size_t)perm_scratch_floats(N) * 4 > BORE_LDS_BYTES ||
                 perm_ints * sizeof(int32_t) > (size_t)STREAM_WS_BYTES))
     return fail(BORE_E_NEEDS_PERM,
                 "fit: the shuffles of %d models x %d epochs x N=%lld rows are not drawn on the device (more rows than "
                 "an LDS ranks, or more than %lld MiB of them): pass explicit shuffles (`perm`, e.g. from "
                 "bore_amd.shuffle.permutations) -- any N then",
                 n_models, epochs, (long long)N, STREAM_WS_BYTES >> 20);
-  a.theta = theta; a.am = adam_m; a.av = adam_v; a.at = (long long *)adam_t;
-  a.X = X; a.z = z; a.epoch_loss = epoch_loss;
-  a.N = (int)N; a.epochs = epochs; a.B = batch_size;
-  a.lr = adam->lr; a.beta1 = adam->beta1; a.beta2 = adam->beta2; a.eps = adam->eps;
+  fit_fill<false>(a, r);
   a.o_g = (long long)stream_tile_floats(L);
   a.ws_stride = a.o_g + (batch_size > BORE_BATCH_MAX ? L.P : 0);
   hipStream_t st = (hipStream_t)stream;
@@ -886,11 +876,10 @@ static int stream_fit(const bore_mlp_desc *desc, int n_models, float *theta, flo
   float *buf = nullptr;
   HIP_TRY(hipMallocAsync((void **)&buf, (ws_floats + perm_ints) * sizeof(float), st));
   a.ws = buf;
-  a.perm = perm;
   int rc = 0;
-  if (!perm) {
+  if (!r.perm) {
     int32_t *drawn = reinterpret_cast<int32_t *>(buf + ws_floats);
-    rc = bore_shuffle_perm(seed, model_index0, n_models, epoch0, epochs, N, drawn, stream);
+    rc = bore_shuffle_perm(r.seed, r.model_index0, n_models, r.epoch0, epochs, N, drawn, stream);
     a.perm = drawn;
   }
   if (rc == 0) {
@@ -906,23 +895,14 @@ extern "C" int bore_mlp_streamed(const bore_mlp_desc *desc) {
   MlpLayout L;
   if (bore_make_layout(desc, 0, BORE_BATCH_MAX, &L)) return fail(BORE_E_INVALID, "bad bore_mlp_desc");
   if (desc->compute != BORE_COMPUTE_F32) return 0;  // (bfloat16: the wide static shapes, never streamed)
-  const bore_batch *batch = g_batch;
-  g_batch = nullptr;  // (the plain entry points' checks)
   int mask = 0;
   if (check_common(desc, 1, 0, BORE_BATCH_MAX, true, BORE_BATCH_MAX + BORE_LAYOUT_FLOATS + 4, &L) == BORE_E_UNSUPPORTED)
     mask |= 1;
   if (check_common(desc, 1, 2, BORE_BATCH_MAX, true, BORE_BATCH_MAX + BORE_LAYOUT_FLOATS + 4, &L) == BORE_E_UNSUPPORTED)
     mask |= 2;
-  {  // (the fit's own check at one row and 64-row batches; it stops at the null pointers when the network fits)
-    FitArgs probe;
-    size_t off = 0;
-    int shape = 0;
-    if (fit_build(desc, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 1, BORE_BATCH_MAX, nullptr, 0, 0, 0,
-                  nullptr, nullptr, probe, off, shape) == BORE_E_UNSUPPORTED)
-      mask |= 4;
-  }
-  g_batch = batch;
-  g_bore_err[0] = 0;
+  FitPlan p;  // (the fit's own capacity check at one row and 64-row batches, outside batch mode)
+  if (fit_plan(desc, 1, 1, BORE_BATCH_MAX, false, nullptr, p) == BORE_E_UNSUPPORTED && !p.fits) mask |= 4;
+  g_bore_err[0] = 0;  // (a refusal above is this query's answer, not its error)
   if (mask)  // (refused by the LDS flavours: inside the streamed flavour's bounds, or the bound by name)
     if (const int rc = stream_bounds(desc, &L)) return rc;
   return mask;

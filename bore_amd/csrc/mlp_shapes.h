@@ -161,6 +161,9 @@ using FitW8Flavours = FlavourList<2, 5, BORE_FIT_SHAPE_16_32, -1, -2, -3, -4>;  
 using WideFlavours = FlavourList<3, 4>;        // bfloat16 kernels, the split screen, the eight-wave restarts
 using NarrowWavesFlavours = FlavourList<2, 5>; // the twelve-wave and the two-per-CU restarts
 using FusedFlavours = FlavourList<1, 5>;       // the fused iteration and work-queue kernels (bore_iter.hip)
+// Is the flavour one of the family's?  (host code that plans for a family's kernel asks the list itself)
+template <int... S>
+static constexpr bool bore_flavour_listed(FlavourList<S...>, int flavour) { return ((flavour == S) || ...); }
 
 // Calls f(std::integral_constant<int, S>{}) for the listed flavour S equal to `flavour` and returns its result; a
 // flavour that is not listed, or that this build leaves out, is refused.  f is instantiated for the flavours that are

@@ -441,8 +441,8 @@ def test_bad_arguments_fail_loudly(gpu):
 
 
 # ---- mixed-precision fit (BASELINE config 5) -------------------------------------------------
-@pytest.mark.parametrize("N", [200, 1500])   # 1500 rows: the shuffle no longer fits beside the bf16-MFMA
-@pytest.mark.parametrize("D,units,acts", [    # kernel's two weight images -> the fp32-MFMA form takes over
+@pytest.mark.parametrize("N", [200, 1500])   # (both in the bf16-MFMA form: an explicit perm of 1500 rows still fits
+@pytest.mark.parametrize("D,units,acts", [    # beside its two weight images; the fp32-MFMA form: the next test)
     (32, [128, 128, 1], ["relu", "relu", "linear"]),          # config 5
     (16, [64, 64, 64, 1], ["relu", "elu", "tanh", "sigmoid"]),  # config 3 shape, mixed activations
 ])
@@ -479,6 +479,34 @@ def test_bf16_fit_tracks_the_bf16_oracle(gpu, D, units, acts, N):
     loss2 = ops.mlp_fit(desc, th2, m2, v2, t2, dev(X[None]), dev(z[None]), E, 64,
                         perm=dev(perms[None], torch.int32))
     assert torch.equal(th, th2) and torch.equal(loss, loss2)
+
+
+def test_bf16_fit_in_its_fp32_mfma_form_tracks_the_bf16_oracle(gpu):
+    """32->128-128-1 with the shuffle drawn on the device at N = 785: the first N whose perm + keys no longer fit
+    beside the bf16-MFMA kernel's weight images (tests/native/fit_plan_dump.hip: 784 rows launch fit_bf16_mfma_kernel,
+    785 fit_bf16_kernel; with an explicit perm the switch is at 3161, so the 1500 rows above stay in the bf16 form).
+    One epoch = 13 Adam steps, the oracle on the host statement of the same shuffle stream; the stated tolerance of
+    test_bf16_fit_tracks_the_bf16_oracle (12 - 24 steps)."""
+    from bore_amd import shuffle
+    rs = np.random.RandomState(5)
+    D, units, acts, N = 32, [128, 128, 1], ["relu", "relu", "linear"], 785
+    p0 = O.glorot_uniform_params(D, units, rs)
+    for i in range(1, len(p0), 2):
+        p0[i] = rs.normal(scale=0.1, size=p0[i].shape).astype(np.float32)
+    X = rs.uniform(size=(N, D)).astype(np.float32)
+    z = (rs.uniform(size=N) < 0.3).astype(np.float32)
+    desc = _lib.make_desc(D, units, acts, compute="bfloat16")
+    th = dev(pack(p0)).reshape(1, -1)
+    m, v = torch.zeros_like(th), torch.zeros_like(th)
+    t = torch.zeros(1, dtype=torch.int64, device=th.device)
+    loss = ops.mlp_fit(desc, th, m, v, t, dev(X[None]), dev(z[None]), 1, 64, seed=21)
+    ref = [q.copy() for q in p0]
+    st = O.AdamState(ref)
+    hist = O.fit_bf16(ref, acts, st, X, z, shuffle.permutations(21, 1, 1, N)[0])
+    assert int(t[0]) == 13 == st.t
+    np.testing.assert_allclose(loss.cpu().numpy()[0], hist, rtol=1e-2)
+    np.testing.assert_allclose(th.cpu().numpy()[0], pack(ref), atol=1.5e-3, rtol=2e-2)
+    np.testing.assert_allclose(m.cpu().numpy()[0], pack(st.m), atol=2e-4, rtol=5e-2)
 
 
 def test_bf16_fit_learns_like_fp32_and_rejects_other_shapes(gpu):
