@@ -18,7 +18,7 @@ CSRC = os.path.join(_HERE, "csrc")
 # only ever LOADED: build_native() writes the default path and nothing else.)
 DEFAULT_LIB_PATH = os.path.join(CSRC, "libbore_hip.so")
 LIB_PATH = os.environ.get("BORE_LIB_PATH") or DEFAULT_LIB_PATH
-SOURCES = ["bore_all.hip"]   # a unity build of bore_{hip,argmax,svgd,iter,engine,lstm,stream}.hip
+SOURCES = ["bore_all.hip"]   # a unity build of bore_{hip,argmax,svgd,iter,engine,lstm,stream,lstm_stream}.hip
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "bore_hip.h")
 
 # The replica engine runs up to a dozen independent launches on as many HIP streams; ROCm gives a
@@ -43,7 +43,8 @@ EXPORTS = [
     "bore_svgd_optimize", "bore_set_batch", "bore_engine_create", "bore_engine_run", "bore_engine_size", "bore_engine_observations",
     "bore_engine_state", "bore_engine_get_stats", "bore_engine_destroy", "bore_objective_branin01",
     "bore_lstm_param_count", "bore_lstm_forward", "bore_lstm_value_and_input_grad", "bore_lstm_fit",
-    "bore_lstm_evaluate", "bore_mlp_streamed",
+    "bore_lstm_evaluate", "bore_lstm_stream_forward", "bore_lstm_stream_value_and_input_grad",
+    "bore_lstm_stream_fit", "bore_lstm_stream_evaluate", "bore_lstm_streamed", "bore_mlp_streamed",
     "bore_stream_screen_topk", "bore_stream_sample_screen_topk", "bore_stream_lbfgsb_minimize",
     "bore_stream_svgd_optimize",
 ]
@@ -246,6 +247,9 @@ def lib():
     L.bore_lstm_fit.argtypes = [lp, i32, vp, vp, vp, vp, vp, vp, i64, i32, f32, i32, i32, vp,
                                 C.POINTER(AdamCfg), vp, vp]
     L.bore_lstm_evaluate.argtypes = [lp, i32, vp, vp, vp, i64, i32, f32, vp, vp, vp]
+    for name in ("forward", "value_and_input_grad", "fit", "evaluate"):
+        getattr(L, "bore_lstm_stream_" + name).argtypes = getattr(L, "bore_lstm_" + name).argtypes
+    L.bore_lstm_streamed.argtypes = [lp, i32]
     L.bore_mlp_streamed.argtypes = [dp]
     L.bore_stream_screen_topk.argtypes = L.bore_screen_topk.argtypes
     L.bore_stream_sample_screen_topk.argtypes = L.bore_sample_screen_topk.argtypes

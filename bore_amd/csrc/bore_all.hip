@@ -8,3 +8,4 @@
 #include "bore_engine.hip"
 #include "bore_lstm.hip"
 #include "bore_stream.hip"
+#include "bore_lstm_stream.hip"

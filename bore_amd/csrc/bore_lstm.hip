@@ -14,6 +14,8 @@
 // per-tile device workspace (stream-ordered, hipMallocAsync), accumulates the weight gradients of an
 // Adam step in a per-model device buffer in a fixed order, and updates theta (LDS), m and v (memory)
 // once per step -- every Adam step of a call inside one launch, as the Dense fit does.
+// This is the LDS flavour: what does not fit one CU's LDS is refused here and taken by the streamed flavour,
+// bore_lstm_stream.hip (entry points of its own), which shares the scalar arithmetic and the packed layout below.
 #include "host_common.h"
 #include "mlp_math.h"
 
@@ -43,7 +45,8 @@ struct Lay {
 // --------------------------------------------------------------------------------------------------
 // host: descriptor -> layout
 // --------------------------------------------------------------------------------------------------
-static int make_lay(const bore_lstm_desc *d, int T, Lay *y) {
+// What holds for either flavour (bore_lstm_stream.hip has bounds of its own): a descriptor of the BORE classifier.
+static int check_desc(const bore_lstm_desc *d) {
   if (!d) return fail(BORE_E_INVALID, "lstm: null descriptor");
   if (d->output_dim != 1)
     return fail(BORE_E_UNSUPPORTED, "lstm: output_dim must be 1 (the BORE classifier), got %d", d->output_dim);
@@ -52,6 +55,29 @@ static int make_lay(const bore_lstm_desc *d, int T, Lay *y) {
                 d->input_dim, d->n_layers, d->units);
   if (d->act < BORE_ACT_LINEAR || d->act > BORE_ACT_TANH)
     return fail(BORE_E_INVALID, "lstm: unknown activation %d", d->act);
+  return 0;
+}
+
+// The network of a checked descriptor and where its pieces start in the packed vector (either flavour).
+static void lay_packed(const bore_lstm_desc *d, int T, Lay &a) {
+  a.D = d->input_dim; a.L = d->n_layers; a.H = d->units; a.act = d->act; a.T = T < 1 ? 1 : T;
+  a.G = 4 * a.H; a.G1 = a.G + 1;
+  long long g = 0;
+  for (int l = 0; l < a.L; ++l) {
+    const int in = l == 0 ? a.D : a.H;
+    a.in_dim[l] = in;
+    a.gW[l] = (int)g; g += (long long)in * a.G;
+    a.gU[l] = (int)g; g += (long long)a.H * a.G;
+    a.gb[l] = (int)g; g += a.G;
+    a.l2k[l] = d->l2_kernel[l]; a.l2b[l] = d->l2_bias[l];
+  }
+  a.gWo = (int)g; g += a.H; a.gbo = (int)g; g += 1;
+  a.l2k[a.L] = d->l2_kernel[a.L]; a.l2b[a.L] = d->l2_bias[a.L];
+  a.P = (int)g;
+}
+
+static int make_lay(const bore_lstm_desc *d, int T, Lay *y) {
+  if (const int rc = check_desc(d)) return rc;
   if (d->input_dim > MAXD)
     return fail(BORE_E_UNSUPPORTED, "lstm: input_dim %d > %d (BORE_LSTM_MAX_INPUT)", d->input_dim, MAXD);
   if (d->n_layers > MAXL)
@@ -61,24 +87,14 @@ static int make_lay(const bore_lstm_desc *d, int T, Lay *y) {
   if (T < 0 || T > MAXT)
     return fail(BORE_E_UNSUPPORTED, "lstm: %d steps > %d (BORE_LSTM_MAX_STEPS)", T, MAXT);
   Lay &a = *y;
-  a.D = d->input_dim; a.L = d->n_layers; a.H = d->units; a.act = d->act; a.T = T < 1 ? 1 : T;
-  a.G = 4 * a.H; a.G1 = a.G + 1;
-  long long g = 0, s = 0;
+  lay_packed(d, T, a);
+  long long s = 0;
   for (int l = 0; l < a.L; ++l) {
-    const int in = l == 0 ? a.D : a.H;
-    a.in_dim[l] = in;
-    a.gW[l] = (int)g; g += (long long)in * a.G;
-    a.gU[l] = (int)g; g += (long long)a.H * a.G;
-    a.gb[l] = (int)g; g += a.G;
-    a.sW[l] = (int)s; s += (long long)in * a.G1;
+    a.sW[l] = (int)s; s += (long long)a.in_dim[l] * a.G1;
     a.sU[l] = (int)s; s += (long long)a.H * a.G1;
     a.sb[l] = (int)s; s += a.G;
-    a.l2k[l] = d->l2_kernel[l]; a.l2b[l] = d->l2_bias[l];
   }
-  a.gWo = (int)g; g += a.H; a.gbo = (int)g; g += 1;
   a.sWo = (int)s; s += a.H; a.sbo = (int)s; s += 1;
-  a.l2k[a.L] = d->l2_kernel[a.L]; a.l2b[a.L] = d->l2_bias[a.L];
-  a.P = (int)g;
   s = (s + 3) & ~3LL;
   const int Dm = a.D > a.H ? a.D : a.H;
   a.o_h = (int)s; s += (long long)a.L * TILE * a.H;
@@ -166,14 +182,20 @@ struct Src {
 
 // mask[b][t] = 1 iff any feature of step t differs from mask_value (Keras Masking); use_mask = 0: all live
 template <typename XT>
+__device__ __forceinline__ bool step_live(const Lay &a, const Src<XT> &src, const int *rows, int b, int t, int use_mask,
+                                          float mask_value) {
+  bool live = !use_mask;
+  if (use_mask)
+    for (int k = 0; k < a.D; ++k) live |= src.x(rows, b, t, k) != mask_value;
+  return live;
+}
+
+template <typename XT>
 __device__ void make_mask(const Lay &a, const Src<XT> &src, const int *rows, int nrows, int T, int use_mask,
                           float mask_value, float *mask) {
   for (int it = threadIdx.x; it < nrows * T; it += NT) {
     const int b = it / T, t = it % T;
-    bool live = !use_mask;
-    if (use_mask)
-      for (int k = 0; k < a.D; ++k) live |= src.x(rows, b, t, k) != mask_value;
-    mask[b * T + t] = live ? 1.f : 0.f;
+    mask[b * T + t] = step_live(a, src, rows, b, t, use_mask, mask_value) ? 1.f : 0.f;
   }
 }
 

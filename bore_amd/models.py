@@ -534,6 +534,12 @@ class _RecurrentNetwork:
     def _ensure_built(self, x=None):
         self.factory._ensure_built(x)
 
+    def _op(self, name, T):
+        """``ops.lstm_<name>`` when the LDS kernels take this network over ``T`` steps, else ``ops.lstm_stream_<name>``
+        (``ops.lstm_streamed``; a network neither takes raises there).  A function of (descriptor, T) alone, so the
+        training network and a one-to-one network of the same T are always served by the same flavour."""
+        return getattr(ops, ("lstm_stream_" if ops.lstm_streamed(self._desc, T) else "lstm_") + name)
+
     def get_weights(self):
         return self.factory.get_weights()
 
@@ -630,9 +636,10 @@ class ManyToManyNetwork(_RecurrentNetwork):
             self.adam_t = torch.zeros(1, dtype=torch.int64, device=self.theta.device)
         P = self._perm(epochs, N, shuffle, perm)
         o = self._optimizer
+        fit_op = self._op("fit", X.shape[2])
 
         def launch(e0, n):
-            loss = ops.lstm_fit(self._desc, self.theta, self.adam_m, self.adam_v, self.adam_t, X, y, n, batch_size,
+            loss = fit_op(self._desc, self.theta, self.adam_m, self.adam_v, self.adam_t, X, y, n, batch_size,
                                 P[:, e0:e0 + n].contiguous(), mask_value=self.mask_value, lr=o.learning_rate,
                                 beta1=o.beta_1, beta2=o.beta_2, eps=o.epsilon)
             self._epochs_seen += n
@@ -669,7 +676,7 @@ class ManyToManyNetwork(_RecurrentNetwork):
         """[loss, accuracy] (loss alone without metrics) under the masking rules of bore_lstm_evaluate."""
         self._check_loss()
         X, y = self._data(x, y)
-        loss, acc = ops.lstm_evaluate(self._desc, self.theta, X, y, mask_value=self.mask_value)
+        loss, acc = self._op("evaluate", X.shape[2])(self._desc, self.theta, X, y, mask_value=self.mask_value)
         if self._metrics:
             return [float(loss[0]), float(acc[0])]
         return float(loss[0])
@@ -677,7 +684,7 @@ class ManyToManyNetwork(_RecurrentNetwork):
     def predict(self, x, batch_size=None, verbose=0, **kwargs):
         """[n, T, D] -> (n, T, 1) float32 logits."""
         X, _ = self._data(x)
-        out = ops.lstm_forward(self._desc, self.theta, X, mask_value=self.mask_value)
+        out = self._op("forward", X.shape[2])(self._desc, self.theta, X, mask_value=self.mask_value)
         return out[0].cpu().numpy()[..., None]
 
     def __call__(self, x, training=False):
@@ -705,7 +712,7 @@ class OneToOneNetwork(_RecurrentNetwork):
         x = np.asarray(x, dtype=np.float32).reshape(-1, int(self.factory.input_dim))
         self._ensure_built(x)
         X = torch.from_numpy(np.ascontiguousarray(x)).to(self.theta.device).reshape(1, x.shape[0], -1)
-        out = ops.lstm_forward(self._desc, self.theta, X, num_steps=self.num_steps)
+        out = self._op("forward", self.num_steps)(self._desc, self.theta, X, num_steps=self.num_steps)
         return out[0].cpu().numpy().reshape(-1, 1)
 
     def __call__(self, x, training=False):
@@ -713,13 +720,15 @@ class OneToOneNetwork(_RecurrentNetwork):
 
     def _value_and_input_grad(self, X, transform, negate):
         """The hook base.convert takes for this network: X [1, R, D] f64 device."""
-        return ops.lstm_value_and_input_grad(self._desc, self.theta, X, self.num_steps, transform, negate)
+        return self._op("value_and_input_grad", self.num_steps)(self._desc, self.theta, X, self.num_steps, transform,
+                                                                negate)
 
 
 class MaximizableOneToOneNetwork(MaximizableMixin, OneToOneNetwork):
     """``MaximizableSequential(transform=...)`` of the one-to-one form: screening through
     bore_lstm_forward and argpartition on the host, the restarts as SciPy's L-BFGS-B state machines
-    advanced together with one bore_lstm_value_and_input_grad launch per round."""
+    advanced together with one bore_lstm_value_and_input_grad launch per round (the bore_lstm_stream_* twins for a
+    network the LDS kernels refuse: ``_RecurrentNetwork._op``)."""
 
     restart_mode = "lockstep"
     screen_mode = "host"

@@ -457,9 +457,7 @@ def lstm_param_count(desc):
     return int(p)
 
 
-def lstm_forward(desc, theta, X, num_steps=None, mask_value=1e9, out=None):
-    """theta [L,P] f32.  X [L,N,T,D] f32 -> logits [L,N,T] (many-to-many, masked by ``mask_value``);
-    X [L,N,D] f32 with ``num_steps`` -> [L,N] (one-to-one: x repeated over the steps, last step)."""
+def _lstm_forward(entry, desc, theta, X, num_steps, mask_value, out):
     L = theta.shape[0]
     D = desc.input_dim
     _chk(theta, torch.float32, (L, lstm_param_count(desc)), "theta")
@@ -480,14 +478,18 @@ def lstm_forward(desc, theta, X, num_steps=None, mask_value=1e9, out=None):
         _chk(out, torch.float32, shape, "out")
     if N == 0:
         return out
-    _lib.check(_lib.lib().bore_lstm_forward(C.byref(desc), L, _lib.ptr(theta), _lib.ptr(X), N, T, int(m2m),
-                                            float(mask_value), _lib.ptr(out), _lib.stream_ptr()))
+    _lib.check(getattr(_lib.lib(), entry)(C.byref(desc), L, _lib.ptr(theta), _lib.ptr(X), N, T, int(m2m),
+                                          float(mask_value), _lib.ptr(out), _lib.stream_ptr()))
     return out
 
 
-def lstm_value_and_input_grad(desc, theta, X, num_steps, transform="identity", negate=True):
-    """theta [L,P] f32; X [L,R,D] f64 -> (val [L,R] f32, grad [L,R,D] f64) of T(+-f(x)), f the
-    one-to-one network over ``num_steps`` steps."""
+def lstm_forward(desc, theta, X, num_steps=None, mask_value=1e9, out=None):
+    """theta [L,P] f32.  X [L,N,T,D] f32 -> logits [L,N,T] (many-to-many, masked by ``mask_value``);
+    X [L,N,D] f32 with ``num_steps`` -> [L,N] (one-to-one: x repeated over the steps, last step)."""
+    return _lstm_forward("bore_lstm_forward", desc, theta, X, num_steps, mask_value, out)
+
+
+def _lstm_value_and_input_grad(entry, desc, theta, X, num_steps, transform, negate):
     L = theta.shape[0]
     D = desc.input_dim
     _chk(theta, torch.float32, (L, lstm_param_count(desc)), "theta")
@@ -501,16 +503,20 @@ def lstm_value_and_input_grad(desc, theta, X, num_steps, transform="identity", n
     grad = torch.empty((L, R, D), dtype=torch.float64, device=theta.device)
     if R == 0:
         return val, grad
-    _lib.check(_lib.lib().bore_lstm_value_and_input_grad(
+    _lib.check(getattr(_lib.lib(), entry)(
         C.byref(desc), L, _lib.ptr(theta), _lib.ptr(X), R, int(num_steps), _lib.TRANSFORM[transform],
         int(bool(negate)), _lib.ptr(val), _lib.ptr(grad), _lib.stream_ptr()))
     return val, grad
 
 
-def lstm_fit(desc, theta, m, v, t, X, y, epochs, batch_size, perm, mask_value=1e9, lr=1e-3, beta1=0.9,
-             beta2=0.999, eps=1e-7, want_loss=True):
-    """In-place fit of L many-to-many networks over X [L,N,T,D] f32, y [L,N,T] f32 with explicit
-    per-epoch permutations perm [L,epochs,N] int32.  Returns epoch_loss [L,epochs] f32 (or None)."""
+def lstm_value_and_input_grad(desc, theta, X, num_steps, transform="identity", negate=True):
+    """theta [L,P] f32; X [L,R,D] f64 -> (val [L,R] f32, grad [L,R,D] f64) of T(+-f(x)), f the
+    one-to-one network over ``num_steps`` steps."""
+    return _lstm_value_and_input_grad("bore_lstm_value_and_input_grad", desc, theta, X, num_steps, transform, negate)
+
+
+def _lstm_fit(entry, desc, theta, m, v, t, X, y, epochs, batch_size, perm, mask_value, lr, beta1, beta2, eps,
+              want_loss):
     L = theta.shape[0]
     D = desc.input_dim
     P = lstm_param_count(desc)
@@ -530,15 +536,22 @@ def lstm_fit(desc, theta, m, v, t, X, y, epochs, batch_size, perm, mask_value=1e
         raise ValueError("perm: entries must lie in [0, N)")
     loss = torch.empty((L, epochs), dtype=torch.float32, device=theta.device) if want_loss else None
     cfg = _lib.AdamCfg(lr, beta1, beta2, eps)
-    _lib.check(_lib.lib().bore_lstm_fit(
+    _lib.check(getattr(_lib.lib(), entry)(
         C.byref(desc), L, _lib.ptr(theta), _lib.ptr(m), _lib.ptr(v), _lib.ptr(t), _lib.ptr(X), _lib.ptr(y), N, T,
         float(mask_value), epochs, int(batch_size), _lib.ptr(perm), C.byref(cfg), _lib.ptr(loss),
         _lib.stream_ptr()))
     return loss
 
 
-def lstm_evaluate(desc, theta, X, y, mask_value=1e9):
-    """X [L,N,T,D] f32, y [L,N,T] f32 -> (loss [L] f32, accuracy [L] f32)."""
+def lstm_fit(desc, theta, m, v, t, X, y, epochs, batch_size, perm, mask_value=1e9, lr=1e-3, beta1=0.9,
+             beta2=0.999, eps=1e-7, want_loss=True):
+    """In-place fit of L many-to-many networks over X [L,N,T,D] f32, y [L,N,T] f32 with explicit
+    per-epoch permutations perm [L,epochs,N] int32.  Returns epoch_loss [L,epochs] f32 (or None)."""
+    return _lstm_fit("bore_lstm_fit", desc, theta, m, v, t, X, y, epochs, batch_size, perm, mask_value, lr, beta1,
+                     beta2, eps, want_loss)
+
+
+def _lstm_evaluate(entry, desc, theta, X, y, mask_value):
     L = theta.shape[0]
     D = desc.input_dim
     _chk(theta, torch.float32, (L, lstm_param_count(desc)), "theta")
@@ -549,6 +562,45 @@ def lstm_evaluate(desc, theta, X, y, mask_value=1e9):
     _chk(y, torch.float32, (L, N, T), "y")
     loss = torch.empty(L, dtype=torch.float32, device=theta.device)
     acc = torch.empty(L, dtype=torch.float32, device=theta.device)
-    _lib.check(_lib.lib().bore_lstm_evaluate(C.byref(desc), L, _lib.ptr(theta), _lib.ptr(X), _lib.ptr(y), N, T,
-                                             float(mask_value), _lib.ptr(loss), _lib.ptr(acc), _lib.stream_ptr()))
+    _lib.check(getattr(_lib.lib(), entry)(C.byref(desc), L, _lib.ptr(theta), _lib.ptr(X), _lib.ptr(y), N, T,
+                                          float(mask_value), _lib.ptr(loss), _lib.ptr(acc), _lib.stream_ptr()))
     return loss, acc
+
+
+def lstm_evaluate(desc, theta, X, y, mask_value=1e9):
+    """X [L,N,T,D] f32, y [L,N,T] f32 -> (loss [L] f32, accuracy [L] f32)."""
+    return _lstm_evaluate("bore_lstm_evaluate", desc, theta, X, y, mask_value)
+
+
+# the streamed flavour (bore_lstm_stream_*): the signatures and results of the four functions above, for any float32
+# network within BORE_LSTM_STREAM_MAX_* -- one that fits LDS as well
+def lstm_streamed(desc, T):
+    """0: the LDS kernels (``lstm_*``) take ``desc`` over ``T`` steps; 1: only the streamed ones (``lstm_stream_*``)
+    do; raises ``UnsupportedError`` naming the bound when neither does.  A host query: no GPU call."""
+    rc = int(_lib.lib().bore_lstm_streamed(C.byref(desc), int(T)))
+    if rc < 0:
+        _lib.check(rc)
+    return rc
+
+
+def lstm_stream_forward(desc, theta, X, num_steps=None, mask_value=1e9, out=None):
+    """``lstm_forward`` on the streamed kernels."""
+    return _lstm_forward("bore_lstm_stream_forward", desc, theta, X, num_steps, mask_value, out)
+
+
+def lstm_stream_value_and_input_grad(desc, theta, X, num_steps, transform="identity", negate=True):
+    """``lstm_value_and_input_grad`` on the streamed kernels."""
+    return _lstm_value_and_input_grad("bore_lstm_stream_value_and_input_grad", desc, theta, X, num_steps, transform,
+                                      negate)
+
+
+def lstm_stream_fit(desc, theta, m, v, t, X, y, epochs, batch_size, perm, mask_value=1e9, lr=1e-3, beta1=0.9,
+                    beta2=0.999, eps=1e-7, want_loss=True):
+    """``lstm_fit`` on the streamed kernels: one workgroup per model."""
+    return _lstm_fit("bore_lstm_stream_fit", desc, theta, m, v, t, X, y, epochs, batch_size, perm, mask_value, lr,
+                     beta1, beta2, eps, want_loss)
+
+
+def lstm_stream_evaluate(desc, theta, X, y, mask_value=1e9):
+    """``lstm_evaluate`` on the streamed kernels."""
+    return _lstm_evaluate("bore_lstm_stream_evaluate", desc, theta, X, y, mask_value)

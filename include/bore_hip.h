@@ -493,17 +493,26 @@ void bore_engine_destroy(bore_engine *engine);
  * mask_value; a masked step keeps h and c and outputs the previous output (Keras RNN over a Masking
  * layer).  Loss: BCE from logits weighted by the mask and divided by ALL n*T elements (TF 2.5
  * SUM_OVER_BATCH_SIZE), plus l2 * sum(w^2) for W and b of every cell (never U) and of the head.
- * Bounds of this build: BORE_LSTM_MAX_* below, and the parameters plus one 64-sequence tile of
- * state in one CU's LDS (160 KB); BORE_E_UNSUPPORTED names the bound otherwise.  The LDS budget is
- * the bound that binds: one layer takes at most 58 units (D = 1, T = 1), 57 at D = 2, 54 at
- * T = 16, 50 at D = 16 and T = 16, so BORE_LSTM_MAX_UNITS itself is never reached.  The plugin
- * default, 2 layers of 32 units, needs 151 376 B at D = 16 and T = 16 (92 % of the budget) and
- * fits up to D = 32; a third layer of 32 units does not fit.  Additive to ABI 12.
+ * Two flavours, each with entry points of its own:
+ *   LDS (bore_lstm_*): the parameters plus one 64-sequence tile of state in one CU's LDS (160 KB).
+ *     Bounds: BORE_LSTM_MAX_* below and that budget; BORE_E_UNSUPPORTED names the bound otherwise.
+ *     The LDS budget is the bound that binds: one layer takes at most 58 units (D = 1, T = 1), 57
+ *     at D = 2, 54 at T = 16, 50 at D = 16 and T = 16, so BORE_LSTM_MAX_UNITS itself is never
+ *     reached.  The plugin default, 2 layers of 32 units, needs 151 376 B at D = 16 and T = 16 (92 %
+ *     of the budget) and fits up to D = 40 at T = 5 and D = 32 at T = 16; a third layer of 32 units
+ *     does not fit.
+ *   streamed (bore_lstm_stream_*, further below): the parameters stay in global memory and every
+ *     gate product runs through the panel product of the Dense streamed flavour.  Bounds:
+ *     BORE_LSTM_STREAM_MAX_UNITS, BORE_LSTM_STREAM_MAX_INPUT, BORE_LSTM_MAX_LAYERS, BORE_LSTM_MAX_STEPS.
+ * bore_lstm_streamed(desc, T) says which one takes a network; bore_amd.models asks it per call and
+ * takes the LDS flavour whenever that one fits.  Additive to ABI 12.
  * --------------------------------------------------------------------------------------------- */
 #define BORE_LSTM_MAX_LAYERS 4
 #define BORE_LSTM_MAX_UNITS 64
 #define BORE_LSTM_MAX_STEPS 16
 #define BORE_LSTM_MAX_INPUT 64
+#define BORE_LSTM_STREAM_MAX_UNITS 128 /* 4H = 512 = BORE_STREAM_MAX_UNITS, the widest panel product */
+#define BORE_LSTM_STREAM_MAX_INPUT 512
 
 typedef struct bore_lstm_desc {
   int32_t input_dim;                         /* D */
@@ -561,6 +570,48 @@ int bore_lstm_fit(const bore_lstm_desc *desc, int n_models, float *theta, float 
 int bore_lstm_evaluate(const bore_lstm_desc *desc, int n_models, const float *theta, const float *X,
                        const float *y, int64_t N, int T, float mask_value, float *loss, float *acc,
                        void *stream);
+
+/*
+ * The streamed flavour of the four entry points above: their argument lists, outputs and semantics (masking, the
+ * loss divisor, l2 on W, b and the head but never on U, epoch_loss, Adam warm start and adam_t).  ANY float32
+ * network with input_dim <= BORE_LSTM_STREAM_MAX_INPUT, units <= BORE_LSTM_STREAM_MAX_UNITS, up to
+ * BORE_LSTM_MAX_LAYERS cells and BORE_LSTM_MAX_STEPS steps, batch_size <= 64 -- one that fits LDS as well, no
+ * switch involved; BORE_E_UNSUPPORTED names the bound otherwise, before any pointer is looked at and before any
+ * HIP call.  theta stays in global memory; a workgroup takes a tile of up to 64 sequences whose state lives in a
+ * stream-ordered workspace, and per (step, cell) the gate pre-activations, their transposed products in the
+ * backward pass and, once per Adam step, the weight gradients are panel products on the matrix cores.
+ *   fit                ONE workgroup per model, every Adam step of the call in one launch: a single model uses one
+ *                      compute unit.  Workspace about 64 T (L (11H + 1) + D + 4) floats per model.
+ *   forward, evaluate, value + input gradient
+ *                      one workgroup per (model, tile); at most 64 MiB of workspace per call (or one tile per
+ *                      model), a workgroup walks several tiles beyond.  evaluate adds its tiles' sums in a second
+ *                      small launch, in tile order.
+ * Within the flavour: one-to-one equals many-to-many at the last step of tiled input, the identity value of
+ * value_and_input_grad equals forward of the fp32-rounded point, a model alone gives the bits of a multi-model
+ * launch, a row alone the bits of a full tile, E + E epochs equal 2E epochs, two runs are identical.  Against the LDS
+ * flavour results agree to float32 rounding, not bit for bit (another order of the sums).
+ * Measured on one MI355X (device events after warm-up, T = 5, one model): per Adam step at N = 64,
+ * batch_size 64: 0.61 ms at 16 -> 2x32 (bore_lstm_fit there: 1.37 ms), 0.70 ms at 48 -> 2x32, 1.58 ms at 16 -> 2x64;
+ * per 1024-row value + input gradient 0.46 / 0.52 / 1.06 ms (LDS: 0.65), per 1024-row forward 0.21 / 0.24 / 0.53 ms
+ * (LDS: 0.22).  Not measured: several models per launch, 16 steps.
+ */
+int bore_lstm_stream_forward(const bore_lstm_desc *desc, int n_models, const float *theta, const float *X,
+                             int64_t n_rows, int T, int many_to_many, float mask_value, float *out,
+                             void *stream);
+int bore_lstm_stream_value_and_input_grad(const bore_lstm_desc *desc, int n_models, const float *theta,
+                                          const double *X, int64_t n_rows, int num_steps, int transform,
+                                          int negate, float *val, double *grad, void *stream);
+int bore_lstm_stream_fit(const bore_lstm_desc *desc, int n_models, float *theta, float *adam_m,
+                         float *adam_v, int64_t *adam_t, const float *X, const float *y, int64_t N, int T,
+                         float mask_value, int epochs, int batch_size, const int32_t *perm,
+                         const bore_adam_cfg *adam, float *epoch_loss, void *stream);
+int bore_lstm_stream_evaluate(const bore_lstm_desc *desc, int n_models, const float *theta, const float *X,
+                              const float *y, int64_t N, int T, float mask_value, float *loss, float *acc,
+                              void *stream);
+
+/* Pure host query, no HIP call: 0 if bore_lstm_* take (desc, T), 1 if only bore_lstm_stream_* do,
+ * BORE_E_INVALID on a bad descriptor or T < 1, BORE_E_UNSUPPORTED (the bound named) if neither flavour does. */
+int bore_lstm_streamed(const bore_lstm_desc *desc, int T);
 
 /* ---------------------------------------------------------------------------------------------
  * Streamed flavour: float32 Dense stacks whose parameters do not fit one workgroup's LDS.  The
