@@ -15,13 +15,14 @@
 // Adam step in a per-model device buffer in a fixed order, and updates theta (LDS), m and v (memory)
 // once per step -- every Adam step of a call inside one launch, as the Dense fit does.
 // This is the LDS flavour: what does not fit one CU's LDS is refused here and taken by the streamed flavour,
-// bore_lstm_stream.hip (entry points of its own), which shares the scalar arithmetic and the packed layout below.
+// bore_lstm_stream.hip (entry points of its own).  The two share the scalar arithmetic of a cell and of the loss
+// (lstm_math.h; the Adam update: mlp_math.h's adam_update_ieee), the packed layout and the request checks below.
 #include "host_common.h"
-#include "mlp_math.h"
+#include "lstm_math.h"
 
 namespace bore_lstm {
 
-using bore::sigmoid_stable, bore::act_grad, bore::bce_loss, bore::accuracy_hit, bore::AdamClock;
+using bore::AdamClock, bore::adam_update_ieee, bore::objective_transform;
 
 constexpr int NT = 512;           // threads per workgroup (8 waves)
 constexpr int TILE = 64;          // sequences per tile (batch_size <= 64)
@@ -45,8 +46,11 @@ struct Lay {
 // --------------------------------------------------------------------------------------------------
 // host: descriptor -> layout
 // --------------------------------------------------------------------------------------------------
-// What holds for either flavour (bore_lstm_stream.hip has bounds of its own): a descriptor of the BORE classifier.
-static int check_desc(const bore_lstm_desc *d) {
+// What either flavour does with a descriptor: a descriptor of the BORE classifier, within the flavour's bounds (`who`:
+// "lstm" / "lstm_stream"; its two maxima and the names of their macros), then the network and where its pieces start
+// in the packed vector.
+static int lay_packed(const bore_lstm_desc *d, int T, const char *who, int max_in, const char *max_in_name, int max_h,
+                      const char *max_h_name, Lay &a) {
   if (!d) return fail(BORE_E_INVALID, "lstm: null descriptor");
   if (d->output_dim != 1)
     return fail(BORE_E_UNSUPPORTED, "lstm: output_dim must be 1 (the BORE classifier), got %d", d->output_dim);
@@ -55,11 +59,12 @@ static int check_desc(const bore_lstm_desc *d) {
                 d->input_dim, d->n_layers, d->units);
   if (d->act < BORE_ACT_LINEAR || d->act > BORE_ACT_TANH)
     return fail(BORE_E_INVALID, "lstm: unknown activation %d", d->act);
-  return 0;
-}
-
-// The network of a checked descriptor and where its pieces start in the packed vector (either flavour).
-static void lay_packed(const bore_lstm_desc *d, int T, Lay &a) {
+  if (d->input_dim > max_in)
+    return fail(BORE_E_UNSUPPORTED, "%s: input_dim %d > %d (%s)", who, d->input_dim, max_in, max_in_name);
+  if (d->n_layers > MAXL)
+    return fail(BORE_E_UNSUPPORTED, "%s: n_layers %d > %d (BORE_LSTM_MAX_LAYERS)", who, d->n_layers, MAXL);
+  if (d->units > max_h) return fail(BORE_E_UNSUPPORTED, "%s: units %d > %d (%s)", who, d->units, max_h, max_h_name);
+  if (T < 0 || T > MAXT) return fail(BORE_E_UNSUPPORTED, "%s: %d steps > %d (BORE_LSTM_MAX_STEPS)", who, T, MAXT);
   a.D = d->input_dim; a.L = d->n_layers; a.H = d->units; a.act = d->act; a.T = T < 1 ? 1 : T;
   a.G = 4 * a.H; a.G1 = a.G + 1;
   long long g = 0;
@@ -74,20 +79,12 @@ static void lay_packed(const bore_lstm_desc *d, int T, Lay &a) {
   a.gWo = (int)g; g += a.H; a.gbo = (int)g; g += 1;
   a.l2k[a.L] = d->l2_kernel[a.L]; a.l2b[a.L] = d->l2_bias[a.L];
   a.P = (int)g;
+  return 0;
 }
 
 static int make_lay(const bore_lstm_desc *d, int T, Lay *y) {
-  if (const int rc = check_desc(d)) return rc;
-  if (d->input_dim > MAXD)
-    return fail(BORE_E_UNSUPPORTED, "lstm: input_dim %d > %d (BORE_LSTM_MAX_INPUT)", d->input_dim, MAXD);
-  if (d->n_layers > MAXL)
-    return fail(BORE_E_UNSUPPORTED, "lstm: n_layers %d > %d (BORE_LSTM_MAX_LAYERS)", d->n_layers, MAXL);
-  if (d->units > MAXH)
-    return fail(BORE_E_UNSUPPORTED, "lstm: units %d > %d (BORE_LSTM_MAX_UNITS)", d->units, MAXH);
-  if (T < 0 || T > MAXT)
-    return fail(BORE_E_UNSUPPORTED, "lstm: %d steps > %d (BORE_LSTM_MAX_STEPS)", T, MAXT);
   Lay &a = *y;
-  lay_packed(d, T, a);
+  if (const int rc = lay_packed(d, T, "lstm", MAXD, "BORE_LSTM_MAX_INPUT", MAXH, "BORE_LSTM_MAX_UNITS", a)) return rc;
   long long s = 0;
   for (int l = 0; l < a.L; ++l) {
     a.sW[l] = (int)s; s += (long long)a.in_dim[l] * a.G1;
@@ -120,17 +117,6 @@ static int make_lay(const bore_lstm_desc *d, int T, Lay *y) {
 // --------------------------------------------------------------------------------------------------
 // device
 // --------------------------------------------------------------------------------------------------
-// act(x); elu through expm1f for x <= 0, NaN in -> NaN out (act_fwd's ReLU, fmaxf, gives 0 for NaN: not the same function)
-__device__ __forceinline__ float actf(int a, float x) {
-  switch (a) {
-    case BORE_ACT_RELU: return x > 0.f ? x : (x == x ? 0.f : x);
-    case BORE_ACT_ELU: return x > 0.f ? x : expm1f(x);
-    case BORE_ACT_SIGMOID: return sigmoid_stable(x);
-    case BORE_ACT_TANH: return tanhf(x);
-    default: return x;
-  }
-}
-
 // LDS address of packed parameter p
 __device__ __forceinline__ int lds_of(const Lay &a, int p) {
   for (int l = 0; l < a.L; ++l) {
@@ -233,19 +219,15 @@ __device__ void tile_forward(const Lay &a, float *sm, const Src<XT> &src, int nr
           const float *w = U + k * G1 + u;
           r0 = fmaf(hv, w[0], r0); r1 = fmaf(hv, w[H], r1); r2 = fmaf(hv, w[2 * H], r2); r3 = fmaf(hv, w[3 * H], r3);
         }
-        const float gi = sigmoid_stable((s0 + r0) + bias[u]);
-        const float gf = sigmoid_stable((s1 + r1) + bias[H + u]);
-        const float gg = actf(a.act, (s2 + r2) + bias[2 * H + u]);
-        const float go = sigmoid_stable((s3 + r3) + bias[3 * H + u]);
-        const float cp = cl[b * H + u], hp = hl[b * H + u];
-        const float c = gf * cp + gi * gg;
-        const float h = go * actf(a.act, c);
-        const bool live = mask[b * T + t] != 0.f;
-        cn[q] = live ? c : cp;
-        hn[q] = live ? h : hp;
+        const Gates g = gates_of(a.act, (s0 + r0) + bias[u], (s1 + r1) + bias[H + u], (s2 + r2) + bias[2 * H + u],
+                                 (s3 + r3) + bias[3 * H + u]);
+        const float cp = cl[b * H + u];
+        // two products and a sum, three roundings; the streamed flavour forms fmaf(f, cp, i * g), two
+        const float c = g.f * cp + g.i * g.g;
+        cell_out(a.act, g.o, c, cp, hl[b * H + u], mask[b * T + t] != 0.f, cn[q], hn[q]);
         if (ws) {
           float *gw = ws + (((long long)l * a.T + t) * TILE + b) * G;
-          gw[u] = gi; gw[H + u] = gf; gw[2 * H + u] = gg; gw[3 * H + u] = go;
+          gw[u] = g.i; gw[H + u] = g.f; gw[2 * H + u] = g.g; gw[3 * H + u] = g.o;
         }
       }
       __syncthreads();
@@ -321,23 +303,13 @@ __device__ void tile_backward(const Lay &a, float *sm, const Src<XT> &src, int n
         const int b = it / H, u = it % H;
         const float above = l == L - 1 ? dlogit[b * T + t] * Wo[u] : din[b * H + u];
         const float dh = dhl[it] + above;
-        const float dcin = dcl[it];
         const bool live = mask[b * T + t] != 0.f;
         const float *g = gts + b * G;
-        const float gi = g[u], gf = g[H + u], gg = g[2 * H + u], go = g[3 * H + u];
-        const float c = ct[it], cp = cpv ? cpv[it] : 0.f;
-        const float ac = actf(a.act, c);
-        const float dct = dcin + dh * go * act_grad(a.act, ac);
-        const float dzi = dct * gg * (gi * (1.f - gi));
-        const float dzf = dct * cp * (gf * (1.f - gf));
-        const float dzg = dct * gi * act_grad(a.act, gg);
-        const float dzo = dh * ac * (go * (1.f - go));
+        const GateDeltas dl = gate_deltas(a.act, Gates{g[u], g[H + u], g[2 * H + u], g[3 * H + u]}, ct[it],
+                                          cpv ? cpv[it] : 0.f, dh, dcl[it], live);
         float *d = dz + b * G;
-        d[u] = live ? dzi : 0.f;
-        d[H + u] = live ? dzf : 0.f;
-        d[2 * H + u] = live ? dzg : 0.f;
-        d[3 * H + u] = live ? dzo : 0.f;
-        dcl[it] = live ? dct * gf : dcin;
+        d[u] = dl.zi; d[H + u] = dl.zf; d[2 * H + u] = dl.zg; d[3 * H + u] = dl.zo;
+        dcl[it] = dl.c;
         if (!live) dhl[it] = dh;  // (a masked step passes h's gradient to the step before)
       }
       __syncthreads();
@@ -399,10 +371,7 @@ __device__ float tile_bce(const Lay &a, float *sm, const float *Y, long long y_s
   for (int it = threadIdx.x; it < nrows * T; it += NT) {
     const int b = it / T, t = it % T;
     const float x = logit[it], y = Y[(long long)rows[b] * y_stride + t];
-    const bool live = mask[it] != 0.f;
-    const float l = bce_loss(x, y);
-    part += live ? l : 0.f;
-    dlogit[it] = live ? (sigmoid_stable(x) - y) * scale : 0.f;
+    part += masked_bce(x, y, mask[it] != 0.f, scale, dlogit[it]);
   }
   return block_sum(part, sm + a.o_red);
 }
@@ -482,15 +451,11 @@ __global__ void __launch_bounds__(NT) lstm_value_grad_kernel(VgArgs A) {
   for (int i = threadIdx.x; i < nrows * T; i += NT) {
     const int b = i / T, t = i % T;
     if (t != T - 1) { dlogit[i] = 0.f; continue; }
-    const float f = logit[i], s = A.negate ? -1.f : 1.f, u = s * f;
-    // objective_transform (mlp_math.h) written out: with the sign inside each arm the identity arm has no multiply,
-    // which the helper's s * dT compiles differently (same values)
-    float v, dv;
-    if (A.transform == BORE_T_SIGMOID) { v = sigmoid_stable(u); dv = s * (v * (1.f - v)); }
-    else if (A.transform == BORE_T_EXP) { v = expf(u); dv = s * v; }
-    else { v = u; dv = s; }
+    const float s = A.negate ? -1.f : 1.f;
+    float v, dT;
+    objective_transform(A.transform, s * logit[i], v, dT);
     A.val[(long long)m * A.n + r0 + b] = v;
-    dlogit[i] = dv;
+    dlogit[i] = s * dT;
   }
   __syncthreads();
   tile_backward(a, sm, src, nrows, T, ws, nullptr, true);
@@ -549,12 +514,9 @@ __global__ void __launch_bounds__(NT) lstm_fit_kernel(FitArgsL A) {
       for (int p = threadIdx.x; p < a.P; p += NT) {
         const int li = lds_of(a, p);
         const float w = sm[li], f = l2_of(a, p);
-        pen = fmaf(f * w, w, pen);
-        const float g = gacc[p] + 2.f * f * w;
+        pen = l2_term(f, w, pen);
         float mm = m_g[p], vv = v_g[p];
-        mm += (g - mm) * omb1;
-        vv += (g * g - vv) * omb2;
-        sm[li] = w - (mm * alpha) / (sqrtf(vv) + A.eps);
+        sm[li] = adam_update_ieee(w, gacc[p], f, mm, vv, alpha, omb1, omb2, A.eps);
         m_g[p] = mm;
         v_g[p] = vv;
         gacc[p] = 0.f;
@@ -605,10 +567,7 @@ __global__ void __launch_bounds__(NT) lstm_evaluate_kernel(EvalArgsL A) {
     float h = 0.f, n = 0.f;
     for (int it = threadIdx.x; it < nrows * T; it += NT) {
       const int b = it / T, t = it % T;
-      const float y = Y[(long long)rows[b] * T + t];
-      const bool live = mask[it] != 0.f;
-      h += live ? accuracy_hit(logit[it], y) : 0.f;
-      n += live ? 1.f : 0.f;
+      masked_hit(logit[it], Y[(long long)rows[b] * T + t], mask[it] != 0.f, h, n);
     }
     const float hs = block_sum(h, sm + a.o_red), ns = block_sum(n, sm + a.o_red);
     tot += (double)bce;
@@ -616,10 +575,7 @@ __global__ void __launch_bounds__(NT) lstm_evaluate_kernel(EvalArgsL A) {
     live_n += (double)ns;
   }
   float pen = 0.f;
-  for (int p = threadIdx.x; p < a.P; p += NT) {
-    const float w = sm[lds_of(a, p)];
-    pen = fmaf(l2_of(a, p) * w, w, pen);
-  }
+  for (int p = threadIdx.x; p < a.P; p += NT) pen = l2_term(l2_of(a, p), sm[lds_of(a, p)], pen);
   const float penalty = block_sum(pen, sm + a.o_red);
   if (threadIdx.x == 0) {
     A.loss[m] = (float)(tot / ((double)N * T)) + penalty;
@@ -646,23 +602,77 @@ extern "C" int64_t bore_lstm_param_count(const bore_lstm_desc *desc) {
   return P + (int64_t)(desc->units + 1) * desc->output_dim;
 }
 
-static int lstm_common(const bore_lstm_desc *desc, int n_models, int T, Lay *a, const char *what) {
-  if (n_models < 1) return fail(BORE_E_INVALID, "%s: n_models must be >= 1 (got %d)", what, n_models);
-  if (T < 1) return fail(BORE_E_INVALID, "%s: need at least one step (got %d)", what, T);
-  return make_lay(desc, T, a);
+// The requests of the four entry-point pairs, whichever flavour runs them (`who` names the entry point, A is the
+// flavour's kernel-argument struct, the other arguments go by their names in include/bore_hip.h).  Refused in this
+// order: n_models, T, the flavour's layout and bounds (`lay`: make_lay / stream_lay into A), pointers, the rest; then
+// A is filled.  Returns 1 when there is nothing to do, else 0 or the error.  No HIP call.
+template <class LayFn>
+static int lstm_common(const char *who, int n_models, int T, LayFn lay) {
+  if (n_models < 1) return fail(BORE_E_INVALID, "%s: n_models must be >= 1 (got %d)", who, n_models);
+  if (T < 1) return fail(BORE_E_INVALID, "%s: need at least one step (got %d)", who, T);
+  return lay();
+}
+
+template <class A, class LayFn>
+static int lstm_forward_request(const char *who, A &a, LayFn lay, int n_models, const float *theta, const float *X,
+                                int64_t n_rows, int T, int many_to_many, float mask_value, float *out) {
+  if (const int rc = lstm_common(who, n_models, T, lay)) return rc;
+  if (!theta || !X || !out) return fail(BORE_E_INVALID, "%s: null pointer", who);
+  if (n_rows < 0) return fail(BORE_E_INVALID, "%s: n_rows < 0", who);
+  a.theta = theta; a.X = X; a.n = n_rows; a.T = T; a.m2m = many_to_many ? 1 : 0;
+  a.use_mask = a.m2m; a.mask_value = mask_value; a.out = out;
+  return n_rows == 0;
+}
+
+// (the sign of the objective stays with the caller: VgArgs::negate, SVgArgs::sign)
+template <class A, class LayFn>
+static int lstm_value_grad_request(const char *who, A &a, LayFn lay, int n_models, const float *theta, const double *X,
+                                   int64_t n_rows, int num_steps, int transform, float *val, double *grad) {
+  if (const int rc = lstm_common(who, n_models, num_steps, lay)) return rc;
+  if (!theta || !X || !val || !grad) return fail(BORE_E_INVALID, "%s: null pointer", who);
+  if (const int rc = check_transform(who, transform)) return rc;
+  if (n_rows < 0) return fail(BORE_E_INVALID, "%s: n_rows < 0", who);
+  a.theta = theta; a.X = X; a.n = n_rows; a.T = num_steps; a.transform = transform; a.val = val; a.grad = grad;
+  return n_rows == 0;
+}
+
+template <class A, class LayFn>
+static int lstm_fit_request(const char *who, A &a, LayFn lay, int n_models, float *theta, float *adam_m, float *adam_v,
+                            int64_t *adam_t, const float *X, const float *y, int64_t N, int T, float mask_value,
+                            int epochs, int batch_size, const int32_t *perm, const bore_adam_cfg *adam,
+                            float *epoch_loss) {
+  if (const int rc = lstm_common(who, n_models, T, lay)) return rc;
+  if (!theta || !adam_m || !adam_v || !adam_t || !X || !y || !adam) return fail(BORE_E_INVALID, "%s: null pointer", who);
+  if (N < 1 || epochs < 0) return fail(BORE_E_INVALID, "%s: N must be >= 1 and epochs >= 0", who);
+  if (batch_size < 1) return fail(BORE_E_INVALID, "%s: batch_size must be >= 1", who);
+  if (batch_size > TILE)
+    return fail(BORE_E_UNSUPPORTED, "%s: batch_size %d > %d (one tile of sequences per Adam step)", who, batch_size, TILE);
+  if (epochs == 0) return 1;
+  if (!perm) return fail(BORE_E_INVALID, "%s: explicit per-epoch permutations are required", who);
+  if (N > 0x7fffffffLL) return fail(BORE_E_UNSUPPORTED, "%s: N > 2^31 - 1", who);
+  a.theta = theta; a.am = adam_m; a.av = adam_v; a.at = (long long *)adam_t; a.X = X; a.Y = y; a.perm = perm;
+  a.epoch_loss = epoch_loss; a.N = N; a.T = T; a.epochs = epochs; a.B = batch_size; a.mask_value = mask_value;
+  a.lr = adam->lr; a.beta1 = adam->beta1; a.beta2 = adam->beta2; a.eps = adam->eps;
+  return 0;
+}
+
+template <class A, class LayFn>
+static int lstm_evaluate_request(const char *who, A &a, LayFn lay, int n_models, const float *theta, const float *X,
+                                 const float *y, int64_t N, int T, float mask_value, float *loss, float *acc) {
+  if (const int rc = lstm_common(who, n_models, T, lay)) return rc;
+  if (!theta || !X || !y || !loss || !acc) return fail(BORE_E_INVALID, "%s: null pointer", who);
+  if (N < 1) return fail(BORE_E_INVALID, "%s: N < 1", who);
+  a.theta = theta; a.X = X; a.Y = y; a.N = N; a.T = T; a.mask_value = mask_value; a.loss = loss; a.acc = acc;
+  return 0;
 }
 
 extern "C" int bore_lstm_forward(const bore_lstm_desc *desc, int n_models, const float *theta, const float *X,
                                  int64_t n_rows, int T, int many_to_many, float mask_value, float *out,
                                  void *stream) {
   FwdArgs A;
-  int rc = lstm_common(desc, n_models, T, &A.a, "lstm_forward");
-  if (rc) return rc;
-  if (!theta || !X || !out) return fail(BORE_E_INVALID, "lstm_forward: null pointer");
-  if (n_rows < 0) return fail(BORE_E_INVALID, "lstm_forward: n_rows < 0");
-  if (n_rows == 0) return 0;
-  A.theta = theta; A.X = X; A.n = n_rows; A.T = T; A.m2m = many_to_many ? 1 : 0;
-  A.use_mask = A.m2m; A.mask_value = mask_value; A.out = out;
+  int rc = lstm_forward_request("lstm_forward", A, [&] { return make_lay(desc, T, &A.a); }, n_models, theta, X, n_rows,
+                                T, many_to_many, mask_value, out);
+  if (rc) return rc < 0 ? rc : 0;
   const size_t bytes = (size_t)A.a.lds_floats * 4;
   rc = allow_lds(lstm_forward_kernel, bytes);
   if (rc) return rc;
@@ -677,16 +687,12 @@ extern "C" int bore_lstm_value_and_input_grad(const bore_lstm_desc *desc, int n_
                                               const double *X, int64_t n_rows, int num_steps, int transform,
                                               int negate, float *val, double *grad, void *stream) {
   VgArgs A;
-  int rc = lstm_common(desc, n_models, num_steps, &A.a, "lstm_value_and_input_grad");
-  if (rc) return rc;
-  if (!theta || !X || !val || !grad) return fail(BORE_E_INVALID, "lstm_value_and_input_grad: null pointer");
-  if ((rc = check_transform("lstm_value_and_input_grad", transform))) return rc;
-  if (n_rows < 0) return fail(BORE_E_INVALID, "lstm_value_and_input_grad: n_rows < 0");
-  if (n_rows == 0) return 0;
+  int rc = lstm_value_grad_request("lstm_value_and_input_grad", A, [&] { return make_lay(desc, num_steps, &A.a); },
+                                   n_models, theta, X, n_rows, num_steps, transform, val, grad);
+  if (rc) return rc < 0 ? rc : 0;
   const long long tiles = (n_rows + TILE - 1) / TILE;
   if (tiles > 0x7fffffffLL) return fail(BORE_E_UNSUPPORTED, "lstm_value_and_input_grad: too many rows");
-  A.theta = theta; A.X = X; A.n = n_rows; A.T = num_steps; A.transform = transform; A.negate = negate ? 1 : 0;
-  A.val = val; A.grad = grad;
+  A.negate = negate ? 1 : 0;
   const size_t bytes = (size_t)A.a.lds_floats * 4;
   rc = allow_lds(lstm_value_grad_kernel, bytes);
   if (rc) return rc;
@@ -704,21 +710,9 @@ extern "C" int bore_lstm_fit(const bore_lstm_desc *desc, int n_models, float *th
                              int epochs, int batch_size, const int32_t *perm, const bore_adam_cfg *adam,
                              float *epoch_loss, void *stream) {
   FitArgsL A;
-  int rc = lstm_common(desc, n_models, T, &A.a, "lstm_fit");
-  if (rc) return rc;
-  if (!theta || !adam_m || !adam_v || !adam_t || !X || !y || !adam)
-    return fail(BORE_E_INVALID, "lstm_fit: null pointer");
-  if (N < 1 || epochs < 0) return fail(BORE_E_INVALID, "lstm_fit: N must be >= 1 and epochs >= 0");
-  if (batch_size < 1) return fail(BORE_E_INVALID, "lstm_fit: batch_size must be >= 1");
-  if (batch_size > TILE)
-    return fail(BORE_E_UNSUPPORTED, "lstm_fit: batch_size %d > %d (one tile of sequences per Adam step)",
-                batch_size, TILE);
-  if (epochs == 0) return 0;
-  if (!perm) return fail(BORE_E_INVALID, "lstm_fit: explicit per-epoch permutations are required");
-  if (N > 0x7fffffffLL) return fail(BORE_E_UNSUPPORTED, "lstm_fit: N > 2^31 - 1");
-  A.theta = theta; A.am = adam_m; A.av = adam_v; A.at = (long long *)adam_t; A.X = X; A.Y = y; A.perm = perm;
-  A.epoch_loss = epoch_loss; A.N = N; A.T = T; A.epochs = epochs; A.B = batch_size; A.mask_value = mask_value;
-  A.lr = adam->lr; A.beta1 = adam->beta1; A.beta2 = adam->beta2; A.eps = adam->eps;
+  int rc = lstm_fit_request("lstm_fit", A, [&] { return make_lay(desc, T, &A.a); }, n_models, theta, adam_m, adam_v,
+                            adam_t, X, y, N, T, mask_value, epochs, batch_size, perm, adam, epoch_loss);
+  if (rc) return rc < 0 ? rc : 0;
   const size_t bytes = (size_t)A.a.lds_floats * 4;
   rc = allow_lds(lstm_fit_kernel, bytes);
   if (rc) return rc;
@@ -742,11 +736,9 @@ extern "C" int bore_lstm_evaluate(const bore_lstm_desc *desc, int n_models, cons
                                   const float *y, int64_t N, int T, float mask_value, float *loss, float *acc,
                                   void *stream) {
   EvalArgsL A;
-  int rc = lstm_common(desc, n_models, T, &A.a, "lstm_evaluate");
+  int rc = lstm_evaluate_request("lstm_evaluate", A, [&] { return make_lay(desc, T, &A.a); }, n_models, theta, X, y, N,
+                                 T, mask_value, loss, acc);
   if (rc) return rc;
-  if (!theta || !X || !y || !loss || !acc) return fail(BORE_E_INVALID, "lstm_evaluate: null pointer");
-  if (N < 1) return fail(BORE_E_INVALID, "lstm_evaluate: N < 1");
-  A.theta = theta; A.X = X; A.Y = y; A.N = N; A.T = T; A.mask_value = mask_value; A.loss = loss; A.acc = acc;
   const size_t bytes = (size_t)A.a.lds_floats * 4;
   rc = allow_lds(lstm_evaluate_kernel, bytes);
   if (rc) return rc;

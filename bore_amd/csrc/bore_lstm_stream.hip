@@ -24,14 +24,17 @@
 // of ONE workgroup through the workspace around __syncthreads() (bore_stream.hip's hand-over rule); no workgroup
 // waits for another one -- evaluate's tiles leave partial sums that a second small kernel adds in tile order.
 //
-// The scalar arithmetic is bore_lstm.hip's and mlp_math.h's: actf, act_grad, sigmoid_stable, bce_loss,
-// accuracy_hit, step_live, objective_transform, AdamClock, l2_of.
+// The scalar arithmetic is the LDS flavour's, each formula defined once: the cell and the masked loss in lstm_math.h
+// (all but the line that forms c: see tile_forward), objective_transform, adam_update_ieee and AdamClock in
+// mlp_math.h, step_live and l2_of in bore_lstm.hip, which also holds the request checks of both flavours.
 
 namespace bore_lstm_stream {
 
-using bore::StreamLds, bore::stream_gemm, bore::wave_sum, bore::objective_transform, bore::STREAM_WS_BYTES;
-using bore_lstm::Lay, bore_lstm::Src, bore_lstm::actf, bore_lstm::l2_of, bore_lstm::step_live;
-using bore::sigmoid_stable, bore::act_grad, bore::bce_loss, bore::accuracy_hit, bore::AdamClock;
+using bore::StreamLds, bore::stream_gemm, bore::stream_wg_sum, bore::objective_transform;
+using bore::AdamClock, bore::adam_update_ieee;
+using bore_lstm::Lay, bore_lstm::Src, bore_lstm::l2_of, bore_lstm::step_live;
+using bore_lstm::Gates, bore_lstm::gates_of, bore_lstm::cell_out, bore_lstm::GateDeltas, bore_lstm::gate_deltas;
+using bore_lstm::masked_bce, bore_lstm::masked_hit, bore_lstm::l2_term;
 
 constexpr int ROWS = bore::SROWS;  // sequences per tile (batch_size <= 64)
 constexpr int MAXL = BORE_LSTM_MAX_LAYERS;
@@ -51,18 +54,9 @@ struct SLay {
 // host: descriptor -> bounds, workspace layout
 // --------------------------------------------------------------------------------------------------
 static int stream_lay(const bore_lstm_desc *d, int T, int mode, SLay *y) {
-  if (const int rc = bore_lstm::check_desc(d)) return rc;
-  if (d->input_dim > BORE_LSTM_STREAM_MAX_INPUT)
-    return fail(BORE_E_UNSUPPORTED, "lstm_stream: input_dim %d > %d (BORE_LSTM_STREAM_MAX_INPUT)", d->input_dim,
-                BORE_LSTM_STREAM_MAX_INPUT);
-  if (d->n_layers > MAXL)
-    return fail(BORE_E_UNSUPPORTED, "lstm_stream: n_layers %d > %d (BORE_LSTM_MAX_LAYERS)", d->n_layers, MAXL);
-  if (d->units > BORE_LSTM_STREAM_MAX_UNITS)
-    return fail(BORE_E_UNSUPPORTED, "lstm_stream: units %d > %d (BORE_LSTM_STREAM_MAX_UNITS)", d->units,
-                BORE_LSTM_STREAM_MAX_UNITS);
-  if (T < 0 || T > BORE_LSTM_MAX_STEPS)
-    return fail(BORE_E_UNSUPPORTED, "lstm_stream: %d steps > %d (BORE_LSTM_MAX_STEPS)", T, BORE_LSTM_MAX_STEPS);
-  bore_lstm::lay_packed(d, T, y->a);
+  if (const int rc = bore_lstm::lay_packed(d, T, "lstm_stream", BORE_LSTM_STREAM_MAX_INPUT, "BORE_LSTM_STREAM_MAX_INPUT",
+                                           BORE_LSTM_STREAM_MAX_UNITS, "BORE_LSTM_STREAM_MAX_UNITS", y->a))
+    return rc;
   const Lay &a = y->a;
   y->keep = mode != WS_FORWARD;
   y->keep_dz = mode == WS_FIT;
@@ -111,16 +105,6 @@ __device__ __forceinline__ float *c_at(const SLay &y, float *ws, int l, int t, i
 }
 __device__ __forceinline__ float *dz_at(const SLay &y, float *ws, int l, int t, int nr) {
   return ws + y.o_dz + (y.keep_dz ? ((long long)l * y.a.T * ROWS + (long long)t * nr) * y.a.G : 0);
-}
-
-// fixed-order sum over the workgroup: the lanes of a wave, then the four waves in order; every work-item gets it
-__device__ __forceinline__ float wg_sum(StreamLds &S, float v) {
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) S.red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const float total = ((S.red[0] + S.red[1]) + S.red[2]) + S.red[3];
-  __syncthreads();
-  return total;
 }
 
 // What a tile needs before its first step: the mask [t][b]; with a backward pass ahead, the 1 columns; and h = 0
@@ -185,17 +169,14 @@ __device__ __forceinline__ void tile_forward(StreamLds &S, const SLay &y, const 
       for (int it = tid; it < nr * H; it += NTH) {
         const int b = it / H, u = it - b * H;
         float *z = Z + b * G;
-        const float gi = sigmoid_stable(z[u]);
-        const float gf = sigmoid_stable(z[H + u]);
-        const float gg = actf(a.act, z[2 * H + u]);
-        const float go = sigmoid_stable(z[3 * H + u]);
-        const float cp = cpv ? cpv[it] : 0.f, hp = xh[b * K1 + in + u];
-        const float c = fmaf(gf, cp, gi * gg);
-        const float h = go * actf(a.act, c);
-        const bool live = mask[t * nr + b] != 0.f;
-        const float cn = live ? c : cp, hn = live ? h : hp;
+        const Gates g = gates_of(a.act, z[u], z[H + u], z[2 * H + u], z[3 * H + u]);
+        const float cp = cpv ? cpv[it] : 0.f;
+        // one product and an fmaf, two roundings; the LDS flavour forms f * cp + i * g, three
+        const float c = fmaf(g.f, cp, g.i * g.g);
+        float cn, hn;
+        cell_out(a.act, g.o, c, cp, xh[b * K1 + in + u], mask[t * nr + b] != 0.f, cn, hn);
         if (keep) {
-          z[u] = gi; z[H + u] = gf; z[2 * H + u] = gg; z[3 * H + u] = go;
+          z[u] = g.i; z[H + u] = g.f; z[2 * H + u] = g.g; z[3 * H + u] = g.o;
         }
         cc[it] = cn;
         if (hnext) hnext[b * K1 + in + u] = hn;
@@ -235,23 +216,12 @@ __device__ __forceinline__ void tile_backward(StreamLds &S, const SLay &y, const
         const int b = it / H, u = it - b * H;
         const float above = l == L - 1 ? dlogit[t * nr + b] * Wo[u] : din[it];
         const float dh = dhl[it] + above;
-        const float dcin = dcl[it];
-        const bool live = mask[t * nr + b] != 0.f;
         const float *g = gts + b * G;
-        const float gi = g[u], gf = g[H + u], gg = g[2 * H + u], go = g[3 * H + u];
-        const float c = ct[it], cp = cpv ? cpv[it] : 0.f;
-        const float ac = actf(a.act, c);
-        const float dct = dcin + dh * go * act_grad(a.act, ac);
-        const float dzi = dct * gg * (gi * (1.f - gi));
-        const float dzf = dct * cp * (gf * (1.f - gf));
-        const float dzg = dct * gi * act_grad(a.act, gg);
-        const float dzo = dh * ac * (go * (1.f - go));
+        const GateDeltas dl = gate_deltas(a.act, Gates{g[u], g[H + u], g[2 * H + u], g[3 * H + u]}, ct[it],
+                                          cpv ? cpv[it] : 0.f, dh, dcl[it], mask[t * nr + b] != 0.f);
         float *d = dz + b * G;
-        d[u] = live ? dzi : 0.f;
-        d[H + u] = live ? dzf : 0.f;
-        d[2 * H + u] = live ? dzg : 0.f;
-        d[3 * H + u] = live ? dzo : 0.f;
-        dcl[it] = live ? dct * gf : dcin;
+        d[u] = dl.zi; d[H + u] = dl.zf; d[2 * H + u] = dl.zg; d[3 * H + u] = dl.zo;
+        dcl[it] = dl.c;
         dhl[it] = dh;  // (a masked step passes h's gradient to the step before; a live one: replaced below)
       }
       __syncthreads();
@@ -284,22 +254,18 @@ __device__ __forceinline__ float tile_bce(StreamLds &S, const SLay &y, float *ws
   for (int it = threadIdx.x; it < nr * T; it += NTH) {
     const int t = it / nr, b = it - t * nr;
     const float x = logit[it], yy = Y[(long long)rows[b] * T + t];
-    const bool live = mask[it] != 0.f;
-    const float l = bce_loss(x, yy);
-    part += live ? l : 0.f;
-    if (scale != 0.f) dlogit[it] = live ? (sigmoid_stable(x) - yy) * scale : 0.f;
+    float d;
+    part += masked_bce(x, yy, mask[it] != 0.f, scale, d);
+    if (scale != 0.f) dlogit[it] = d;
   }
-  return wg_sum(S, part);
+  return stream_wg_sum(S, part);
 }
 
 // sum of l2 factor x w^2 over the packed vector (never U: l2_of); every work-item gets it
 __device__ __forceinline__ float tile_penalty(StreamLds &S, const Lay &a, const float *th) {
   float pen = 0.f;
-  for (int p = threadIdx.x; p < a.P; p += NTH) {
-    const float w = th[p];
-    pen = fmaf(l2_of(a, p) * w, w, pen);
-  }
-  return wg_sum(S, pen);
+  for (int p = threadIdx.x; p < a.P; p += NTH) pen = l2_term(l2_of(a, p), th[p], pen);
+  return stream_wg_sum(S, pen);
 }
 
 __device__ __forceinline__ bool any_l2(const Lay &a) {
@@ -459,12 +425,8 @@ __global__ void __launch_bounds__(NTH) lstm_stream_fit_kernel(const SFitArgs A) 
       ++steps;
       const float alpha = clock.advance(A.lr, A.beta1, A.beta2);
       auto adam = [&](const int p, const float f, const float grad) {
-        const float w = th[p];
-        const float g = grad + 2.f * f * w;
         float mm = mg[p], vv = vg[p];
-        mm += (g - mm) * omb1;
-        vv += (g * g - vv) * omb2;
-        th[p] = w - (mm * alpha) / (sqrtf(vv) + eps);
+        th[p] = adam_update_ieee(th[p], grad, f, mm, vv, alpha, omb1, omb2, eps);
         mg[p] = mm;
         vg[p] = vv;
       };
@@ -529,12 +491,9 @@ __global__ void __launch_bounds__(NTH) lstm_stream_evaluate_kernel(const SEvalAr
     float h = 0.f, n = 0.f;
     for (int it = tid; it < nr * T; it += NTH) {
       const int t = it / nr, b = it - t * nr;
-      const float yy = Y[(long long)rows[b] * T + t];
-      const bool live = mask[it] != 0.f;
-      h += live ? accuracy_hit(logit[it], yy) : 0.f;
-      n += live ? 1.f : 0.f;
+      masked_hit(logit[it], Y[(long long)rows[b] * T + t], mask[it] != 0.f, h, n);
     }
-    const float hs = wg_sum(S, h), ns = wg_sum(S, n);
+    const float hs = stream_wg_sum(S, h), ns = stream_wg_sum(S, n);
     if (tid == 0) {
       float *p = A.part + (m * n_tiles + tile) * 3;
       p[0] = bce; p[1] = hs; p[2] = ns;
@@ -567,24 +526,6 @@ __global__ void __launch_bounds__(NTH) lstm_stream_evaluate_finish_kernel(const 
 // --------------------------------------------------------------------------------------------------
 namespace bls = bore_lstm_stream;
 
-static int lstm_stream_common(const bore_lstm_desc *desc, int n_models, int T, int mode, bls::SLay *y, const char *what) {
-  if (n_models < 1) return fail(BORE_E_INVALID, "%s: n_models must be >= 1 (got %d)", what, n_models);
-  if (T < 1) return fail(BORE_E_INVALID, "%s: need at least one step (got %d)", what, T);
-  return bls::stream_lay(desc, T, mode, y);
-}
-
-// Tile walkers per model: two workgroups per CU's worth in flight, never more than there are tiles, and never more
-// than STREAM_WS_BYTES of workspace per call (one tile per model at least), as the Dense streamed rows kernels.
-static long long lstm_stream_walkers(int n_models, long long tiles, long long ws_floats) {
-  long long gy = tiles;
-  const long long cap = (2 * device_cus() + n_models - 1) / n_models;
-  if (gy > cap) gy = cap;
-  const long long by_bytes = bls::STREAM_WS_BYTES / ((long long)n_models * ws_floats * (long long)sizeof(float));
-  if (gy > by_bytes) gy = by_bytes;
-  if (gy > 65535) gy = 65535;
-  return gy < 1 ? 1 : gy;
-}
-
 extern "C" int bore_lstm_streamed(const bore_lstm_desc *desc, int T) {
   if (T < 1) return fail(BORE_E_INVALID, "lstm_streamed: need at least one step (got %d)", T);
   Lay a;
@@ -600,13 +541,11 @@ extern "C" int bore_lstm_stream_forward(const bore_lstm_desc *desc, int n_models
                                         int64_t n_rows, int T, int many_to_many, float mask_value, float *out,
                                         void *stream) {
   bls::SFwdArgs A;
-  if (const int rc = lstm_stream_common(desc, n_models, T, bls::WS_FORWARD, &A.y, "lstm_stream_forward")) return rc;
-  if (!theta || !X || !out) return fail(BORE_E_INVALID, "lstm_stream_forward: null pointer");
-  if (n_rows < 0) return fail(BORE_E_INVALID, "lstm_stream_forward: n_rows < 0");
-  if (n_rows == 0) return 0;
-  A.theta = theta; A.X = X; A.n = n_rows; A.T = T; A.m2m = many_to_many ? 1 : 0;
-  A.use_mask = A.m2m; A.mask_value = mask_value; A.out = out;
-  const long long gy = lstm_stream_walkers(n_models, (n_rows + bls::ROWS - 1) / bls::ROWS, A.y.ws_floats);
+  const int rc = lstm_forward_request(
+      "lstm_stream_forward", A, [&] { return bls::stream_lay(desc, T, bls::WS_FORWARD, &A.y); }, n_models, theta, X,
+      n_rows, T, many_to_many, mask_value, out);
+  if (rc) return rc < 0 ? rc : 0;
+  const long long gy = stream_walkers(n_models, (n_rows + bls::ROWS - 1) / bls::ROWS, A.y.ws_floats, true);
   hipStream_t st = (hipStream_t)stream;
   HIP_TRY(hipMallocAsync((void **)&A.ws, (size_t)n_models * gy * A.y.ws_floats * sizeof(float), st));
   hipLaunchKernelGGL(bls::lstm_stream_forward_kernel, dim3(n_models, (unsigned)gy), dim3(bls::NTH), 0, st, A);
@@ -620,15 +559,12 @@ extern "C" int bore_lstm_stream_value_and_input_grad(const bore_lstm_desc *desc,
                                                      const double *X, int64_t n_rows, int num_steps, int transform,
                                                      int negate, float *val, double *grad, void *stream) {
   bls::SVgArgs A;
-  int rc = lstm_stream_common(desc, n_models, num_steps, bls::WS_VALUE_GRAD, &A.y, "lstm_stream_value_and_input_grad");
-  if (rc) return rc;
-  if (!theta || !X || !val || !grad) return fail(BORE_E_INVALID, "lstm_stream_value_and_input_grad: null pointer");
-  if ((rc = check_transform("lstm_stream_value_and_input_grad", transform))) return rc;
-  if (n_rows < 0) return fail(BORE_E_INVALID, "lstm_stream_value_and_input_grad: n_rows < 0");
-  if (n_rows == 0) return 0;
-  A.theta = theta; A.X = X; A.n = n_rows; A.T = num_steps; A.transform = transform; A.sign = negate ? -1.f : 1.f;
-  A.val = val; A.grad = grad;
-  const long long gy = lstm_stream_walkers(n_models, (n_rows + bls::ROWS - 1) / bls::ROWS, A.y.ws_floats);
+  const int rc = lstm_value_grad_request(
+      "lstm_stream_value_and_input_grad", A, [&] { return bls::stream_lay(desc, num_steps, bls::WS_VALUE_GRAD, &A.y); },
+      n_models, theta, X, n_rows, num_steps, transform, val, grad);
+  if (rc) return rc < 0 ? rc : 0;
+  A.sign = negate ? -1.f : 1.f;
+  const long long gy = stream_walkers(n_models, (n_rows + bls::ROWS - 1) / bls::ROWS, A.y.ws_floats, true);
   hipStream_t st = (hipStream_t)stream;
   HIP_TRY(hipMallocAsync((void **)&A.ws, (size_t)n_models * gy * A.y.ws_floats * sizeof(float), st));
   hipLaunchKernelGGL(bls::lstm_stream_value_grad_kernel, dim3(n_models, (unsigned)gy), dim3(bls::NTH), 0, st, A);
@@ -643,20 +579,10 @@ extern "C" int bore_lstm_stream_fit(const bore_lstm_desc *desc, int n_models, fl
                                     float mask_value, int epochs, int batch_size, const int32_t *perm,
                                     const bore_adam_cfg *adam, float *epoch_loss, void *stream) {
   bls::SFitArgs A;
-  if (const int rc = lstm_stream_common(desc, n_models, T, bls::WS_FIT, &A.y, "lstm_stream_fit")) return rc;
-  if (!theta || !adam_m || !adam_v || !adam_t || !X || !y || !adam)
-    return fail(BORE_E_INVALID, "lstm_stream_fit: null pointer");
-  if (N < 1 || epochs < 0) return fail(BORE_E_INVALID, "lstm_stream_fit: N must be >= 1 and epochs >= 0");
-  if (batch_size < 1) return fail(BORE_E_INVALID, "lstm_stream_fit: batch_size must be >= 1");
-  if (batch_size > bls::ROWS)
-    return fail(BORE_E_UNSUPPORTED, "lstm_stream_fit: batch_size %d > %d (one tile of sequences per Adam step)",
-                batch_size, bls::ROWS);
-  if (epochs == 0) return 0;
-  if (!perm) return fail(BORE_E_INVALID, "lstm_stream_fit: explicit per-epoch permutations are required");
-  if (N > 0x7fffffffLL) return fail(BORE_E_UNSUPPORTED, "lstm_stream_fit: N > 2^31 - 1");
-  A.theta = theta; A.am = adam_m; A.av = adam_v; A.at = (long long *)adam_t; A.X = X; A.Y = y; A.perm = perm;
-  A.epoch_loss = epoch_loss; A.N = N; A.T = T; A.epochs = epochs; A.B = batch_size; A.mask_value = mask_value;
-  A.lr = adam->lr; A.beta1 = adam->beta1; A.beta2 = adam->beta2; A.eps = adam->eps;
+  const int rc = lstm_fit_request(
+      "lstm_stream_fit", A, [&] { return bls::stream_lay(desc, T, bls::WS_FIT, &A.y); }, n_models, theta, adam_m, adam_v,
+      adam_t, X, y, N, T, mask_value, epochs, batch_size, perm, adam, epoch_loss);
+  if (rc) return rc < 0 ? rc : 0;
   hipStream_t st = (hipStream_t)stream;
   HIP_TRY(hipMallocAsync((void **)&A.ws, (size_t)n_models * A.y.ws_floats * sizeof(float), st));
   hipLaunchKernelGGL(bls::lstm_stream_fit_kernel, dim3(n_models), dim3(bls::NTH), 0, st, A);
@@ -670,13 +596,13 @@ extern "C" int bore_lstm_stream_evaluate(const bore_lstm_desc *desc, int n_model
                                          const float *y, int64_t N, int T, float mask_value, float *loss, float *acc,
                                          void *stream) {
   bls::SEvalArgs A;
-  if (const int rc = lstm_stream_common(desc, n_models, T, bls::WS_FORWARD, &A.y, "lstm_stream_evaluate")) return rc;
-  if (!theta || !X || !y || !loss || !acc) return fail(BORE_E_INVALID, "lstm_stream_evaluate: null pointer");
-  if (N < 1) return fail(BORE_E_INVALID, "lstm_stream_evaluate: N < 1");
+  if (const int rc = lstm_evaluate_request(
+          "lstm_stream_evaluate", A, [&] { return bls::stream_lay(desc, T, bls::WS_FORWARD, &A.y); }, n_models, theta, X,
+          y, N, T, mask_value, loss, acc))
+    return rc;
   if (N > 0x7fffffffLL) return fail(BORE_E_UNSUPPORTED, "lstm_stream_evaluate: N > 2^31 - 1");
-  A.theta = theta; A.X = X; A.Y = y; A.N = N; A.T = T; A.mask_value = mask_value; A.loss = loss; A.acc = acc;
   const long long tiles = (N + bls::ROWS - 1) / bls::ROWS;
-  const long long gy = lstm_stream_walkers(n_models, tiles, A.y.ws_floats);
+  const long long gy = stream_walkers(n_models, tiles, A.y.ws_floats, true);
   const size_t n_ws = (size_t)n_models * gy * A.y.ws_floats, n_part = (size_t)n_models * tiles * 3;
   hipStream_t st = (hipStream_t)stream;
   float *buf = nullptr;

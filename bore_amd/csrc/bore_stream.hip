@@ -189,8 +189,19 @@ __device__ __forceinline__ void stream_backward_layer(StreamLds &S, const MlpLay
       });
 }
 
-// sum over l of l2_w[l] |W_l|^2 + l2_b[l] |b_l|^2: per-lane strided sums, a fixed tree over the lanes, then
-// the four waves in order.  Called by the whole workgroup after a barrier; every work-item gets the value.
+// Fixed-order sum over a workgroup of BORE_THREADS: a fixed tree over the lanes of a wave, then the four waves in
+// order.  Called by the whole workgroup; every work-item gets the value.  Ends with a barrier.
+__device__ __forceinline__ float stream_wg_sum(StreamLds &S, float v) {
+  v = wave_sum(v);
+  if ((threadIdx.x & 63) == 0) S.red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  const float total = ((S.red[0] + S.red[1]) + S.red[2]) + S.red[3];
+  __syncthreads();
+  return total;
+}
+
+// sum over l of l2_w[l] |W_l|^2 + l2_b[l] |b_l|^2: per-lane strided sums, then stream_wg_sum.  Called by the whole
+// workgroup after a barrier; every work-item gets the value.
 __device__ __forceinline__ float stream_penalty(StreamLds &S, const MlpLayout &L, const float *th) {
   const int tid = threadIdx.x, nthr = blockDim.x;
   float reg = 0.f;
@@ -207,12 +218,7 @@ __device__ __forceinline__ float stream_penalty(StreamLds &S, const MlpLayout &L
         reg = fmaf(lb * w, w, reg);
       }
   }
-  reg = wave_sum(reg);
-  if ((tid & 63) == 0) S.red[tid >> 6] = reg;
-  __syncthreads();
-  const float total = ((S.red[0] + S.red[1]) + S.red[2]) + S.red[3];
-  __syncthreads();
-  return total;
+  return stream_wg_sum(S, reg);
 }
 
 // ---------------------------------------------------------------------------
@@ -779,6 +785,19 @@ static bool stream_forced(const bore_mlp_desc *desc) {
   return stream_within_bounds(desc);
 }
 
+// Workgroups per model that walk its `tiles` row tiles (or groups of restarts), `ws_floats` of workspace each: with
+// `cu_cap` two per CU's worth over the models, never more than there is work, never more than STREAM_WS_BYTES of
+// workspace per call (one per model at least: 64 MiB is 512 at 8->256-256-1 and 32 at eight layers of 512), <= 65535.
+static long long stream_walkers(int n_models, long long tiles, long long ws_floats, bool cu_cap) {
+  long long gy = tiles;
+  const long long cap = cu_cap ? (2 * device_cus() + n_models - 1) / n_models : gy;
+  if (gy > cap) gy = cap;
+  const long long by_bytes = STREAM_WS_BYTES / ((long long)n_models * ws_floats * (long long)sizeof(float));
+  if (gy > by_bytes) gy = by_bytes;
+  if (gy > 65535) gy = 65535;
+  return gy < 1 ? 1 : gy;
+}
+
 static int stream_rows(bool with_grad, const bore_mlp_desc *desc, int n_models, const float *theta, const float *Xf,
                        const double *Xd, int64_t n_rows, int x_shared, int transform, float sign, float *out,
                        double *grad, void *stream) {
@@ -792,17 +811,8 @@ static int stream_rows(bool with_grad, const bore_mlp_desc *desc, int n_models, 
   if (n_rows == 0) return 0;
   a.theta = theta; a.Xf = Xf; a.Xd = Xd; a.out = out; a.grad = grad;
   a.n_rows = n_rows; a.x_shared = x_shared; a.transform = transform; a.sign = sign;
-  // two workgroups per CU's worth of tiles in flight, never more than there is work, and never more than
-  // STREAM_WS_BYTES of workspace per call (a workgroup walks several tiles then): 64 MiB is 512 workgroups at
-  // 8->256-256-1 and 32 at eight layers of 512
   a.ws_stride = (long long)stream_tile_floats(a.L);
-  long long gy = (n_rows + SROWS - 1) / SROWS;
-  const long long cap = (2 * device_cus() + n_models - 1) / n_models;
-  if (gy > cap) gy = cap;
-  const long long by_bytes = STREAM_WS_BYTES / ((long long)n_models * a.ws_stride * (long long)sizeof(float));
-  if (gy > by_bytes) gy = by_bytes;
-  if (gy > 65535) gy = 65535;
-  if (gy < 1) gy = 1;
+  const long long gy = stream_walkers(n_models, (n_rows + SROWS - 1) / SROWS, a.ws_stride, true);
   hipStream_t st = (hipStream_t)stream;
   HIP_TRY(hipMallocAsync((void **)&a.ws, (size_t)n_models * gy * a.ws_stride * sizeof(float), st));
   const dim3 grid(n_models, (unsigned)gy);
@@ -953,12 +963,8 @@ static int stream_screen(const char *who, const bore_mlp_desc *desc, int n_model
   a.theta = theta; a.Xf = nullptr; a.Xd = X_init; a.grad = nullptr;
   a.n_rows = n_samples; a.x_shared = x_shared; a.transform = 0; a.sign = 1.f;
   a.ws_stride = (long long)stream_tile_floats(a.L);
-  long long gy = (n_samples + SROWS - 1) / SROWS;
-  const long long cap = (2 * device_cus() + n_models - 1) / n_models;
-  if (gy > cap) gy = cap;
-  const long long by_bytes = STREAM_WS_BYTES / ((long long)n_models * a.ws_stride * (long long)sizeof(float));
-  if (gy > by_bytes) gy = by_bytes;
-  if (gy < 1) gy = 1;
+  // (the rule's clamp to 65535 never binds here: n_samples <= BORE_STREAM_MAX_SAMPLES = 16384 is at most 256 tiles)
+  const long long gy = stream_walkers(n_models, (n_samples + SROWS - 1) / SROWS, a.ws_stride, true);
   hipStream_t st = (hipStream_t)stream;
   const size_t ws_floats = (size_t)n_models * gy * a.ws_stride;
   const size_t pred_floats = pred ? 0 : (size_t)n_models * n_samples;
@@ -1040,11 +1046,7 @@ extern "C" int bore_stream_lbfgsb_minimize(const bore_mlp_desc *desc, int n_mode
   // workspaces of all would take more than STREAM_WS_BYTES
   a.ws_stride = (long long)stream_tile_floats(a.L);
   const long long groups = ((long long)num_starts + waves - 1) / waves;
-  long long gy = groups;
-  const long long by_bytes = STREAM_WS_BYTES / ((long long)n_models * a.ws_stride * (long long)sizeof(float));
-  if (gy > by_bytes) gy = by_bytes;
-  if (gy > 65535) gy = 65535;
-  if (gy < 1) gy = 1;
+  const long long gy = stream_walkers(n_models, groups, a.ws_stride, false);  // (the restarts take no CU cap)
   // every round serves one request of every live problem: a wave's problems, one after another, each within the
   // optimiser's own limit (lbfgsb_build's cap)
   a.max_rounds = ((groups + gy - 1) / gy) * ((long long)opts->maxfun + opts->maxls + 64);

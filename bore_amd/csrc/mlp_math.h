@@ -118,6 +118,15 @@ __device__ __forceinline__ float adam_update(float w, float g, float &m, float &
   v += (g * g - v) * omb2;
   return fmaf(-(m * alpha), fit_rcp(fit_sqrt(v) + eps), w);
 }
+// The same in the IEEE form (the LSTM fits): division and sqrtf, and the gradient 2 f w of the weight's l2 penalty
+// (factor f) added to `grad` first.
+__device__ __forceinline__ float adam_update_ieee(float w, float grad, float f, float &m, float &v, float alpha,
+                                                  float omb1, float omb2, float eps) {
+  const float g = grad + 2.f * f * w;
+  m += (g - m) * omb1;
+  v += (g * g - v) * omb2;
+  return w - (m * alpha) / (sqrtf(v) + eps);
+}
 
 // Step size of Adam step t: lr * sqrt(1 - beta2^t) / (1 - beta1^t), from running beta powers in fp64
 // that are rounded to fp32 at use (DESIGN.md "Adam").  Starts at the t0 steps a model has behind it.
