@@ -46,7 +46,7 @@ EXPORTS = [
     "bore_lstm_evaluate", "bore_lstm_stream_forward", "bore_lstm_stream_value_and_input_grad",
     "bore_lstm_stream_fit", "bore_lstm_stream_evaluate", "bore_lstm_streamed", "bore_mlp_streamed",
     "bore_stream_screen_topk", "bore_stream_sample_screen_topk", "bore_stream_lbfgsb_minimize",
-    "bore_stream_svgd_optimize",
+    "bore_stream_svgd_optimize", "bore_lstm_stream_screen_topk", "bore_lstm_stream_lbfgsb_minimize",
 ]
 
 
@@ -255,6 +255,9 @@ def lib():
     L.bore_stream_sample_screen_topk.argtypes = L.bore_sample_screen_topk.argtypes
     L.bore_stream_lbfgsb_minimize.argtypes = L.bore_lbfgsb_minimize.argtypes
     L.bore_stream_svgd_optimize.argtypes = L.bore_svgd_optimize.argtypes
+    L.bore_lstm_stream_screen_topk.argtypes = [lp, i32, vp, vp, i64, i32, i32, i32, vp, vp, vp, vp]
+    L.bore_lstm_stream_lbfgsb_minimize.argtypes = [lp, i32, vp, i32, i32, i32, vp, i32, dpp, dpp,
+                                                   C.POINTER(LbfgsbOpts), vp, vp, vp, vp, vp]
     for name in EXPORTS:
         if name not in ("bore_last_error", "bore_param_count", "bore_lstm_param_count", "bore_engine_size",
                         "bore_engine_destroy", "bore_set_batch"):

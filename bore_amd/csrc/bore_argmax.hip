@@ -1135,17 +1135,11 @@ __global__ __launch_bounds__(3 * BORE_THREADS) void lbfgsb_kernel_w12(const Lbfg
 
 // The argument checks of the restart entry points and what they convert: the box (nbd: 0 unbounded, 1 lower, 2 both,
 // 3 upper, as lbfgsb.h takes it) and SciPy's options as the optimiser's.  One definition for bore_lbfgsb_minimize and
-// the streamed flavour's bore_stream_lbfgsb_minimize (bore_stream.hip).  No HIP call.
-static int lbfgsb_check_args(const bore_mlp_desc *desc, int n_models, const float *theta, int transform,
-                             const double *x0, int num_starts, const double *lb, const double *ub,
-                             const bore_lbfgsb_opts *opts, const double *x, const double *fun, const double *jac,
-                             const int32_t *info, BoxArgs &box, int *nbd, lbfgsb::Options &opt) {
-  if (!desc || !theta || !x0 || !lb || !ub || !opts || !x || !fun || !jac || !info)
-    return fail(BORE_E_INVALID, "lbfgsb_minimize: null pointer");
-  if (n_models < 1) return fail(BORE_E_INVALID, "n_models must be >= 1 (got %d)", n_models);
-  const int D = desc->input_dim;
-  if (D < 1 || D > BORE_DIM_MAX)
-    return fail(BORE_E_UNSUPPORTED, "lbfgsb_minimize: input_dim must be 1..%d", BORE_DIM_MAX);
+// the streamed flavour's bore_stream_lbfgsb_minimize (bore_stream.hip).  No HIP call.  lbfgsb_convert is the part
+// that looks at no network and at no device pointer (D <= BORE_DIM_MAX and lb, ub, opts not null are the caller's to
+// see to): what the recurrent classifier's bore_lstm_stream_lbfgsb_minimize (bore_lstm_stream.hip) takes as well.
+static int lbfgsb_convert(int D, int transform, int num_starts, const double *lb, const double *ub,
+                          const bore_lbfgsb_opts *opts, BoxArgs &box, int *nbd, lbfgsb::Options &opt) {
   if (num_starts < 1) return fail(BORE_E_INVALID, "lbfgsb_minimize: num_starts < 1");
   if (const int rc = check_transform("lbfgsb_minimize", transform)) return rc;
   if (opts->maxcor < 1 || opts->maxcor > 32)
@@ -1169,6 +1163,19 @@ static int lbfgsb_check_args(const bore_mlp_desc *desc, int n_models, const floa
   opt.maxfun = opts->maxfun;
   opt.maxls = opts->maxls;
   return 0;
+}
+
+static int lbfgsb_check_args(const bore_mlp_desc *desc, int n_models, const float *theta, int transform,
+                             const double *x0, int num_starts, const double *lb, const double *ub,
+                             const bore_lbfgsb_opts *opts, const double *x, const double *fun, const double *jac,
+                             const int32_t *info, BoxArgs &box, int *nbd, lbfgsb::Options &opt) {
+  if (!desc || !theta || !x0 || !lb || !ub || !opts || !x || !fun || !jac || !info)
+    return fail(BORE_E_INVALID, "lbfgsb_minimize: null pointer");
+  if (n_models < 1) return fail(BORE_E_INVALID, "n_models must be >= 1 (got %d)", n_models);
+  const int D = desc->input_dim;
+  if (D < 1 || D > BORE_DIM_MAX)
+    return fail(BORE_E_UNSUPPORTED, "lbfgsb_minimize: input_dim must be 1..%d", BORE_DIM_MAX);
+  return lbfgsb_convert(D, transform, num_starts, lb, ub, opts, box, nbd, opt);
 }
 
 static int lbfgsb_build(const bore_mlp_desc *desc, int n_models, const float *theta,

@@ -100,8 +100,7 @@ class MaximizableMixin:
         self._ensure_built(X0)
         x0 = torch.from_numpy(np.ascontiguousarray(X0, dtype=np.float64)[None]).to(self.theta.device)
         tr = self._func_min.transform
-        # (a network too large for one workgroup's LDS: the same optimiser around the streamed kernels)
-        restarts = ops.stream_lbfgsb_minimize if self._streamed() else ops.lbfgsb_minimize
+        _, restarts = self._device_ops()
         x, fun, jac, info = restarts(self._desc, self.theta, x0, low, high, tr.name, tr.negate, **options)
         x, fun, jac, info = (t[0] for t in ops.lbfgsb_results_to_host(x, fun, jac, info))
         return self._results(x, fun, jac, info, range(len(X0)))
@@ -148,9 +147,7 @@ class MaximizableMixin:
         Xd = torch.empty((num_samples, dim), dtype=torch.float64, device=dev)
         Xd.copy_(xs, non_blocking=True)
         st[4].record()
-        streamed = self._streamed()              # (too large for one workgroup's LDS: the streamed kernels' forms)
-        screen = ops.stream_screen_topk if streamed else ops.screen_topk
-        restarts = ops.stream_lbfgsb_minimize if streamed else ops.lbfgsb_minimize
+        screen, restarts = self._device_ops()
         x0, idx, pred = screen(self._desc, self.theta, Xd, num_starts, want_pred=True)
         st[0][:num_samples].copy_(pred[0], non_blocking=True)
         st[1][:num_starts].copy_(idx[0], non_blocking=True)
@@ -166,6 +163,20 @@ class MaximizableMixin:
             return f_init, None                   # (a tie across the cut: the literal form decides)
         x, fun, jac, info = (t[0] for t in ops.lbfgsb_results_to_host(x, fun, jac, info))
         return f_init, self._results(x, fun, jac, info, [where[int(r)] for r in order])
+
+    def _device_ops(self):
+        """The two callables of the device route: ``screen(desc, theta, X, num_starts, want_pred=...)`` and
+        ``restarts(desc, theta, x0, low, high, transform, negate, **options)``.  A Dense stack takes the LDS kernels'
+        (``ops.screen_topk``, ``ops.lbfgsb_minimize``), one too large for one workgroup's LDS the streamed kernels' forms
+        of the same optimiser; a model of another family overrides this (``MaximizableOneToOneNetwork``)."""
+        from . import ops
+        if self._streamed():
+            return ops.stream_screen_topk, ops.stream_lbfgsb_minimize
+        return ops.screen_topk, ops.lbfgsb_minimize
+
+    def _screening_refused(self, error):
+        """The device screening refused the request (``error``) and ``predict`` + ``argpartition`` take it: silent
+        here -- the restarts below say why, or take the device all the same."""
 
     def _streamed(self, x=None):
         """Does value + input gradient of this model run on the streamed kernels (a float32 network too large for
@@ -222,8 +233,9 @@ class MaximizableMixin:
             from ._lib import UnsupportedError
             try:
                 f_init, results = self._maxima_on_device(X_init, bounds, num_starts, dict(options or {}))
-            except UnsupportedError:
+            except UnsupportedError as e:
                 f_init = None                          # (the literal form below says why, or takes another route)
+                self._screening_refused(e)
         if f_init is None:
             f_init = -self.predict(X_init).squeeze(axis=-1)
 

@@ -6,6 +6,8 @@ same method names, argument meaning and defaults for the subset on the hot path.
 """
 from __future__ import annotations
 
+import warnings
+
 import numpy as np
 import torch
 
@@ -506,10 +508,17 @@ class StackedRecurrentFactory:
         logits, for fit / evaluate."""
         return ManyToManyNetwork(self, mask_value)
 
-    def build_one_to_one(self, num_steps, transform=None):
+    def build_one_to_one(self, num_steps, transform=None, acquisition="lockstep"):
         """RepeatVector(num_steps) -> RNN x L (the last without sequences) -> Dense: [n, D] -> [n, 1], a
-        maximizable network (predict / maxima / argmax)."""
-        return MaximizableOneToOneNetwork(transform, self, num_steps)
+        maximizable network (predict / maxima / argmax).  ``acquisition`` (an extension): "lockstep" (default) --
+        screening through ``predict`` and the restarts as SciPy's state machines on the host; "device" -- both on the
+        device (``MaximizableOneToOneNetwork``: restart_mode = screen_mode = "device")."""
+        if acquisition not in ("lockstep", "device"):
+            raise ValueError(f"acquisition must be 'lockstep' or 'device', got {acquisition!r}")
+        net = MaximizableOneToOneNetwork(transform, self, num_steps)
+        if acquisition == "device":
+            net.restart_mode = net.screen_mode = "device"
+        return net
 
 
 class _RecurrentNetwork:
@@ -728,10 +737,40 @@ class MaximizableOneToOneNetwork(MaximizableMixin, OneToOneNetwork):
     """``MaximizableSequential(transform=...)`` of the one-to-one form: screening through
     bore_lstm_forward and argpartition on the host, the restarts as SciPy's L-BFGS-B state machines
     advanced together with one bore_lstm_value_and_input_grad launch per round (the bore_lstm_stream_* twins for a
-    network the LDS kernels refuse: ``_RecurrentNetwork._op``)."""
+    network the LDS kernels refuse: ``_RecurrentNetwork._op``).
+
+    OPT-IN, ``restart_mode = screen_mode = "device"`` (``build_one_to_one(acquisition="device")``): screening and
+    every restart's L-BFGS-B on the device, two calls per ``maxima`` (bore_lstm_stream_screen_topk,
+    bore_lstm_stream_lbfgsb_minimize; up to 64 input dimensions and 16 384 candidates).  Those are the STREAMED
+    kernels for every network, so a network that fits LDS is optimised on another f/g flavour than ``predict``'s
+    (equal to float32 rounding, not bit for bit) -- one reason the class defaults stay what they were.  What the
+    kernels refuse, a callable transform and a method other than L-BFGS-B take the default route with a
+    ``RuntimeWarning`` that names the reason: the caller asked for the device."""
 
     restart_mode = "lockstep"
     screen_mode = "host"
+
+    def _device_ops(self):
+        T = self.num_steps
+
+        def screen(desc, theta, X_init, num_starts, want_pred=False):
+            return ops.lstm_stream_screen_topk(desc, theta, X_init, num_starts, T, want_pred=want_pred)
+
+        def restarts(desc, theta, x0, low, high, transform="identity", negate=True, **options):
+            return ops.lstm_stream_lbfgsb_minimize(desc, theta, x0, low, high, T, transform, negate, **options)
+
+        return screen, restarts
+
+    def _screening_refused(self, error):
+        warnings.warn(f"screen_mode='device' cannot take this request ({error}); screening through predict and "
+                      "argpartition on the host instead", RuntimeWarning, stacklevel=3)
+
+    def _minimize_from(self, X0, bounds, method, options):
+        if method != "L-BFGS-B" and self.restart_mode == "device":
+            warnings.warn(f"restart_mode='device' runs L-BFGS-B only (got method={method!r}); running "
+                          "scipy.optimize.minimize on the host around the f/g kernel instead", RuntimeWarning,
+                          stacklevel=3)
+        return super()._minimize_from(X0, bounds, method, options)
 
 
 __all__ = ["Sequential", "DenseSequential", "Model", "MaximizableModel", "MaximizableSequential",

@@ -184,18 +184,20 @@ def uniform_candidates(seed, n_models, n_samples, low, high, model_index0=0, dra
     return X
 
 
-def _screen_topk(entry, desc, theta, X_init, num_starts, want_pred):
+def _screen_topk(entry, desc, theta, X_init, num_starts, want_pred, count=param_count, steps=()):
+    """``count``: the descriptor's parameter count; ``steps``: (T,) for the recurrent entry point, which takes it in
+    front of num_starts."""
     L, P = theta.shape
     D = desc.input_dim
     shared = X_init.dim() == 2
     Ns = X_init.shape[-2]
-    _chk(theta, torch.float32, (L, param_count(desc)), "theta")
+    _chk(theta, torch.float32, (L, count(desc)), "theta")
     _chk(X_init, torch.float64, (Ns, D) if shared else (L, Ns, D), "X_init")
     R = int(num_starts)
     x0 = torch.empty((L, R, D), dtype=torch.float64, device=theta.device)
     idx = torch.empty((L, R), dtype=torch.int32, device=theta.device)
     pred = torch.empty((L, Ns), dtype=torch.float32, device=theta.device) if (want_pred or Ns >= 1024) else None
-    _lib.check(entry(C.byref(desc), L, _lib.ptr(theta), _lib.ptr(X_init), Ns, int(shared), R, _lib.ptr(x0),
+    _lib.check(entry(C.byref(desc), L, _lib.ptr(theta), _lib.ptr(X_init), Ns, int(shared), *steps, R, _lib.ptr(x0),
                      _lib.ptr(idx), _lib.ptr(pred), _lib.stream_ptr()))
     return (x0, idx, pred) if want_pred else (x0, idx)
 
@@ -250,10 +252,13 @@ def stream_sample_screen_topk(desc, theta, seed, n_samples, low, high, num_start
 
 
 def _lbfgsb_minimize(entry, desc, theta, x0, low, high, transform="identity", negate=True, maxcor=10,
-                     ftol=2.2204460492503131e-09, gtol=1e-5, maxfun=15000, maxiter=15000, maxls=20):
+                     ftol=2.2204460492503131e-09, gtol=1e-5, maxfun=15000, maxiter=15000, maxls=20,
+                     count=param_count, steps=()):
+    """``count``: the descriptor's parameter count; ``steps``: (T,) for the recurrent entry point, which takes it in
+    front of the transform."""
     L, P = theta.shape
     D = desc.input_dim
-    _chk(theta, torch.float32, (L, param_count(desc)), "theta")
+    _chk(theta, torch.float32, (L, count(desc)), "theta")
     if x0.dim() != 3:
         raise ValueError("x0: expected [n_models, num_starts, D]")
     R = x0.shape[1]
@@ -274,7 +279,7 @@ def _lbfgsb_minimize(entry, desc, theta, x0, low, high, transform="identity", ne
     if R == 0:
         return x, fun, jac, info
     _lib.check(entry(
-        C.byref(desc), L, _lib.ptr(theta), _lib.TRANSFORM[transform], int(bool(negate)),
+        C.byref(desc), L, _lib.ptr(theta), *steps, _lib.TRANSFORM[transform], int(bool(negate)),
         _lib.ptr(x0), R, lo_p, hi_p, C.byref(opts), _lib.ptr(x), _lib.ptr(fun), _lib.ptr(jac),
         _lib.ptr(info), _lib.stream_ptr()))
     return x, fun, jac, info
@@ -604,3 +609,21 @@ def lstm_stream_fit(desc, theta, m, v, t, X, y, epochs, batch_size, perm, mask_v
 def lstm_stream_evaluate(desc, theta, X, y, mask_value=1e9):
     """``lstm_evaluate`` on the streamed kernels."""
     return _lstm_evaluate("bore_lstm_stream_evaluate", desc, theta, X, y, mask_value)
+
+
+# the acquisition of the one-to-one network on the streamed kernels (bore_lstm_stream_screen_topk /
+# _lbfgsb_minimize): opt-in in bore_amd.models (``acquisition="device"``)
+def lstm_stream_screen_topk(desc, theta, X_init, num_starts, num_steps, want_pred=False):
+    """``stream_screen_topk`` for the one-to-one recurrent network over ``num_steps`` steps (D <= 64, at most 16 384
+    candidates): X_init [L,Ns,D] or shared [Ns,D], f64 -> (x0 [L,R,D] f64, idx [L,R] int32[, pred [L,Ns] f32]);
+    ``pred`` is ``lstm_stream_forward(num_steps=num_steps)`` of the float32-cast candidates, bit for bit."""
+    return _screen_topk(_lib.lib().bore_lstm_stream_screen_topk, desc, theta, X_init, num_starts, want_pred,
+                        count=lstm_param_count, steps=(int(num_steps),))
+
+
+def lstm_stream_lbfgsb_minimize(desc, theta, x0, low, high, num_steps, transform="identity", negate=True, **options):
+    """``stream_lbfgsb_minimize`` for the one-to-one recurrent network over ``num_steps`` steps (D <= 64).  The same
+    packed results (``lbfgsb_results_to_host``: one copy); every record is the host build of the optimiser fed
+    ``lstm_stream_value_and_input_grad``'s f and g, bit for bit."""
+    return _lbfgsb_minimize(_lib.lib().bore_lstm_stream_lbfgsb_minimize, desc, theta, x0, low, high, transform, negate,
+                            count=lstm_param_count, steps=(int(num_steps),), **options)

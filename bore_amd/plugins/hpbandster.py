@@ -189,6 +189,8 @@ class SequenceClassifierConfigGenerator(_GeneratorBase):
         self.ftol = optimizer_kws.get("ftol", 1e-9)
         self.max_iter = optimizer_kws.get("max_iter", 1000)
         self.distortion = optimizer_kws.get("distortion")
+        # (an extension: "device" runs screening and restarts of every argmax on the device, build_one_to_one)
+        self.acquisition = optimizer_kws.get("acquisition", "lockstep")
         self.record = MultiFidelityRecord(gamma=gamma)
         self.seed = seed
         self.random_state = np.random.RandomState(seed)
@@ -242,7 +244,9 @@ class SequenceClassifierConfigGenerator(_GeneratorBase):
         self.logger.debug(f"Rung {t} is the highest with at least {self.num_random_init} observations.")
         self._update_classifier()
         if t not in self.funcs:
-            self.funcs[t] = self.model_factory.build_one_to_one(t + 1, transform=self.transform)
+            # (the default goes unsaid: a factory without the extension keeps working)
+            route = {} if self.acquisition == "lockstep" else dict(acquisition=self.acquisition)
+            self.funcs[t] = self.model_factory.build_one_to_one(t + 1, transform=self.transform, **route)
         func = self.funcs[t]
         opt = func.argmax(self.bounds, num_starts=self.num_starts, num_samples=self.num_samples,
                           method=self.method, options=dict(maxiter=self.max_iter, ftol=self.ftol),
@@ -277,7 +281,7 @@ class BOREHyperband(_HyperBand):
                  random_rate=0.1, retrain=False, num_starts=5, num_samples=1024, batch_size=64,
                  num_steps_per_iter=1000, num_epochs=None, optimizer="adam", mask_value=-1., num_layers=2,
                  num_units=32, activation="elu", l2_factor=None, transform="sigmoid", method="L-BFGS-B",
-                 max_iter=1000, ftol=1e-9, distortion=None, seed=None, **kwargs):
+                 max_iter=1000, ftol=1e-9, distortion=None, seed=None, acquisition="lockstep", **kwargs):
         if gamma is None:
             gamma = 1 / eta
         cg = SequenceClassifierConfigGenerator(
@@ -287,7 +291,8 @@ class BOREHyperband(_HyperBand):
                                 activation=activation, optimizer=optimizer, mask_value=mask_value),
             fit_kws=dict(batch_size=batch_size, num_steps_per_iter=num_steps_per_iter, num_epochs=num_epochs),
             optimizer_kws=dict(transform=transform, method=method, max_iter=max_iter, ftol=ftol,
-                               distortion=distortion, num_starts=num_starts, num_samples=num_samples),
+                               distortion=distortion, num_starts=num_starts, num_samples=num_samples,
+                               acquisition=acquisition),
             seed=seed)
         if HAVE_HPBANDSTER:                             # pragma: no cover
             super(_HyperBand, self).__init__(config_generator=cg, **kwargs)   # grandparent: Master

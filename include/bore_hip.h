@@ -690,6 +690,42 @@ int bore_stream_svgd_optimize(const bore_mlp_desc *desc, int n_models, const flo
                               const double *x_init, int n_particles, const double *lb, const double *ub,
                               const bore_svgd_opts *opts, double *x_out, void *stream);
 
+/*
+ * The acquisition of the recurrent classifier's one-to-one network (x repeated over T steps, the logit of the last
+ * step) on the streamed LSTM kernels: bore_stream_screen_topk's and bore_stream_lbfgsb_minimize's argument lists,
+ * outputs and semantics, plus T.  Additive to ABI 12.  OPT-IN: bore_amd.models takes them only where the caller asks
+ * (StackedRecurrentFactory.build_one_to_one(acquisition="device"), BOREHyperband(acquisition="device")); the default
+ * route -- bore_lstm[_stream]_forward, argpartition and SciPy's L-BFGS-B on the host -- is unchanged.  ANY network
+ * within the streamed LSTM bounds, one that fits LDS as well.  Refused before any device pointer is looked at and
+ * before any HIP call, in this order: n_models, T (1..BORE_LSTM_MAX_STEPS), the streamed bounds by name, an input
+ * dimension above BORE_DIM_MAX, n_samples outside 1..BORE_STREAM_MAX_SAMPLES, num_starts outside 1..n_samples (the
+ * restarts: < 1), the options and the box (bore_lbfgsb_minimize's verdicts and texts), null pointers.
+ *   screening  two launches on the stream: bore_lstm_stream_forward's one-to-one form (its geometry and workspace
+ *              rule) over the fp64 candidates, cast to fp32 on the device as Keras casts them, into `pred` --
+ *              stream-ordered scratch when pred == NULL -- bit for bit bore_lstm_stream_forward(num_steps = T) of the
+ *              float32-cast candidates; then the Dense flavour's selection stage (descending prediction, ties to the
+ *              lower row; the chosen rows gathered in fp64).  X_init [n_models][n_samples][D], or one [n_samples][D]
+ *              with x_shared.  No sampled form.
+ *   restarts   one launch; one problem per wave at a time, up to four per workgroup (as many as have room for their
+ *              workspace in LDS beside the panels), wave w of workgroup b taking the model's restarts
+ *              (b + k gridDim.y) waves + w; the workgroup's pending points evaluated by ONE pass of
+ *              bore_lstm_stream_value_and_input_grad's own sequence per round.  Every record equals the host build
+ *              of lbfgsb.h fed that entry point's f and g, bit for bit, whatever the geometry.  Workspace per
+ *              workgroup, stream-ordered: that entry point's tile (at 64 -> 4 x 64 over 16 steps 1 966 080 floats)
+ *              plus 8 D + 4 floats for the points and values; at most 64 MiB per call (or one workgroup per model),
+ *              fewer workgroups each walking several groups of restarts beyond.  A problem the round cap
+ *              ((maxfun + maxls + 64) x a wave's problems) would cut off is reported with status 2.
+ * Resource usage of the two kernels: profiles/lstm/acq_resource_usage.txt; measured against the default route:
+ * profiles/lstm/lstm_acq_time.json.
+ */
+int bore_lstm_stream_screen_topk(const bore_lstm_desc *desc, int n_models, const float *theta,
+                                 const double *X_init, int64_t n_samples, int x_shared, int T,
+                                 int num_starts, double *x0, int32_t *idx, float *pred, void *stream);
+int bore_lstm_stream_lbfgsb_minimize(const bore_lstm_desc *desc, int n_models, const float *theta, int T,
+                                     int transform, int negate, const double *x0, int num_starts,
+                                     const double *lb, const double *ub, const bore_lbfgsb_opts *opts,
+                                     double *x, double *fun, double *jac, int32_t *info, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
