@@ -30,6 +30,7 @@
 
 #include "../../include/bore_hip.h"
 #include "host_common.h"
+#include "mlp_shapes.h"
 
 namespace {
 
@@ -163,6 +164,10 @@ struct bore_engine {
   bore_engine_stats st;
   std::vector<double> y_tmp;
   Async *as = nullptr;  // asynchronous mode (cfg.async_loops)
+  // The screening and the restarts of the lock-step chain (enqueue): the LDS forms, or their streamed twins for a
+  // float32 network too large for one workgroup's LDS -- the same argument lists.  Decided once, at create.
+  decltype(&bore_sample_screen_topk) screen = bore_sample_screen_topk;
+  decltype(&bore_lbfgsb_minimize) restarts = bore_lbfgsb_minimize;
   // set when a run stopped half-way (objective error, watchdog, HIP error): loops are then at
   // different iteration counts and some device-side updates have no host-side record, so the
   // engine refuses further use instead of silently diverging
@@ -239,13 +244,13 @@ int enqueue(bore_engine *e, Group &g) {
   const int64_t steps = (N + c.batch_size - 1) / c.batch_size;
   e->st.fit_bytes += (double)Lg * c.epochs * (4.0 * N * (D + 1) + steps * 24.0 * e->P);
   g.epochs_seen += c.epochs;
-  if ((rc = bore_sample_screen_topk(&e->desc, Lg, th, c.seed, c.loop_id0 + g.a, g.draws, c.num_samples,
-                                    e->low.data(), e->high.data(), R, g.x0, g.idx, nullptr, sp)))
+  if ((rc = e->screen(&e->desc, Lg, th, c.seed, c.loop_id0 + g.a, g.draws, c.num_samples, e->low.data(),
+                      e->high.data(), R, g.x0, g.idx, nullptr, sp)))
     return rc;
   ++g.draws;
   HIP_TRY(hipEventRecord(g.ev[2], g.stream));
-  if ((rc = bore_lbfgsb_minimize(&e->desc, Lg, th, c.transform, 1, g.x0, R, e->low.data(),
-                                 e->high.data(), &c.lbfgsb, g.x, g.fun, g.jac, g.info, sp)))
+  if ((rc = e->restarts(&e->desc, Lg, th, c.transform, 1, g.x0, R, e->low.data(), e->high.data(), &c.lbfgsb, g.x,
+                        g.fun, g.jac, g.info, sp)))
     return rc;
   HIP_TRY(hipEventRecord(g.ev[3], g.stream));
   if ((rc = bore_select_best(Lg, R, D, g.x, g.fun, g.info, c.deduplicate ? g.X_seen : nullptr, g.n,
@@ -1068,6 +1073,22 @@ extern "C" int bore_engine_create(const bore_mlp_desc *desc, const bore_engine_c
   if (L < 1 || cfg->groups < 1 || cfg->n_init < 1 || cfg->epochs < 1 || cfg->num_starts < 1 ||
       cfg->num_samples < cfg->num_starts || !cfg->low || !cfg->high || D < 1 || D > BORE_DIM_MAX)
     return fail(BORE_E_INVALID, "engine_create: bad configuration");
+  // Which kernels take this network -- asked here, before any HIP call: a refusal inside the first bore_engine_run
+  // would come half-way through an iteration and poison the engine.  The model API's rule (MaximizableMixin._streamed):
+  // a float32 network whose value + input gradient does not fit one workgroup's LDS screens and restarts on the
+  // streamed kernels; one that fits neither flavour is refused with the bound named.
+  const int streamed = bore_mlp_streamed(desc);
+  if (streamed < 0) return streamed;
+  g_bore_err[0] = 0;  // (as the query itself leaves it when it answers 0)
+  const bool bf16 = desc->compute == BORE_COMPUTE_BF16;
+  if (cfg->async_loops && (bf16 || (streamed & 2)))
+    return fail(BORE_E_UNSUPPORTED,
+                "engine_create: the asynchronous schedule launches in batch mode (bore_set_batch), which the bfloat16 "
+                "fit and the streamed kernels refuse -- run %s network on the lock-step schedule (async_loops = 0)",
+                bf16 ? "a bfloat16" : "a streamed");
+  if (bf16 && !bore_shape_is_wide(bore_match_shape(desc))) return fail(BORE_E_UNSUPPORTED, kBf16Shapes);
+  if (bf16 && cfg->batch_size != BORE_BATCH_MAX)
+    return fail(BORE_E_UNSUPPORTED, kBf16BatchSize, BORE_BATCH_MAX, cfg->batch_size);
   bore_engine *e = new (std::nothrow) bore_engine();
   if (!e) return fail(BORE_E_HIP, "engine_create: out of memory");
   e->desc = *desc;
@@ -1080,6 +1101,10 @@ extern "C" int bore_engine_create(const bore_mlp_desc *desc, const bore_engine_c
   e->cfg.high = e->high.data();
   e->objective = objective;
   e->user = user;
+  if (streamed & 2) {
+    e->screen = bore_stream_sample_screen_topk;
+    e->restarts = bore_stream_lbfgsb_minimize;
+  }
   std::memset(&e->st, 0, sizeof(e->st));
   e->rs.resize(L);
   for (int l = 0; l < L; ++l) {

@@ -2585,7 +2585,7 @@ static int fit_bf16_impl(const FitRequest &r, void *stream) {
   FitBf16Args a;
   const int64_t N = r.N;
   if (r.batch_size != BORE_BATCH_MAX)
-    return fail(BORE_E_UNSUPPORTED, "fit_bf16: batch_size must be %d (got %d)", BORE_BATCH_MAX, r.batch_size);
+    return fail(BORE_E_UNSUPPORTED, kBf16BatchSize, BORE_BATCH_MAX, r.batch_size);
   if (N < 1 || N > (1 << 20)) return fail(BORE_E_INVALID, "fit_bf16: N=%lld out of range", (long long)N);
   if (r.epochs < 0) return fail(BORE_E_INVALID, "fit_bf16: epochs < 0");
   if (r.n_models < 1) return fail(BORE_E_INVALID, "n_models must be >= 1 (got %d)", r.n_models);

@@ -155,6 +155,8 @@ inline int big_pool(size_t per_slot_doubles, BigPool *out) {
 static const char kBf16Shapes[] =
     "compute = bfloat16 is available for the wide static shapes only (16->64-64-64-1, "
     "32->128-128-1; any activations, no l2)";
+// (the bfloat16 fit's one batch size: fit_bf16_impl, and the engine, which asks before its first launch)
+static const char kBf16BatchSize[] = "fit_bf16: batch_size must be %d (got %d)";
 
 inline int check_common(const bore_mlp_desc *desc, int n_models, int with_deltas, int max_rows,
                         bool may_shrink, size_t extra_floats, MlpLayout *L) {

@@ -87,8 +87,14 @@ class NativeEngine:
                  transform="identity", gamma=0.25, epochs=200, batch_size=64, num_starts=3,
                  num_samples=1024, n_init=10, objective=branin01, options=None, device=None,
                  seed=0, groups=4, deduplicate=False, async_loops=False, resident_wait_us=None,
-                 worker_streams=None, work_queue=None):
-        """async_loops: every loop advances on its own (a loop re-enters the next launch as soon
+                 worker_streams=None, work_queue=None, compute="float32"):
+        """compute: "float32", or "bfloat16" for the two wide shapes on the bf16 matrix cores (16->64-64-64-1,
+        32->128-128-1; batch_size 64).  The lock-step schedule runs every network the model API runs: a float32
+        network too large for one workgroup's LDS screens and restarts on the streamed kernels (``ops.mlp_streamed``).
+        The asynchronous schedule launches in batch mode, which the bfloat16 fit and the streamed kernels refuse: such
+        an engine with ``async_loops=True`` raises ``UnsupportedError``.
+
+        async_loops: every loop advances on its own (a loop re-enters the next launch as soon
         as ITS restarts are done instead of waiting for the slowest loop of its group); same
         trajectories, tested.  Needs num_starts <= 16.  Its knobs (None = the library's default; bore_engine_cfg,
         ABI 12 -- environment variables until round 5): ``resident_wait_us`` how long a loop's workgroup waits on its
@@ -101,7 +107,7 @@ class NativeEngine:
             "loop ids must be consecutive (the device streams are keyed by first id + offset)"
         self.D = D = int(input_dim)
         self.units, self.acts = list(units), list(acts)
-        self.desc = _lib.make_desc(D, self.units, self.acts)
+        self.desc = _lib.make_desc(D, self.units, self.acts, compute=compute)
         self.P = ops.param_count(self.desc)
         tr = resolve(transform).negated()
         assert tr.name is not None, "the native engine runs on the device only: a named transform ('identity', 'sigmoid', 'exp')"
@@ -332,8 +338,10 @@ class ReplicaEngine:
                  transform="identity", gamma=0.25, epochs=200, batch_size=64, num_starts=3,
                  num_samples=1024, n_init=10, objective=branin01, max_points=None,
                  options=None, device=None, mode="device", seed=0, groups=1, select="device",
-                 deduplicate=False):
-        """mode "device": label, fit, candidate draw, screening and all L-BFGS-B restarts run
+                 deduplicate=False, compute="float32"):
+        """compute: as ``NativeEngine``'s ("bfloat16": the two wide shapes, batch_size 64).
+
+        mode "device": label, fit, candidate draw, screening and all L-BFGS-B restarts run
         as five launches per BO iteration with ONE host sync (candidates from the device
         counter stream).  mode "lockstep": candidates from each loop's numpy RandomState and
         SciPy's L-BFGS-B on the host around the batched f/g kernel (the reference's streams
@@ -363,8 +371,17 @@ class ReplicaEngine:
             "loop ids must be consecutive (the device streams are keyed by first id + offset)"
         self.D = D = int(input_dim)
         self.units, self.acts = list(units), list(acts)
-        self.desc = _lib.make_desc(D, self.units, self.acts)
+        self.desc = _lib.make_desc(D, self.units, self.acts, compute=compute)
         self.P = ops.param_count(self.desc)
+        # the device chain's screening and restarts (_enqueue): the LDS forms, or the streamed twins of the same
+        # argument lists for a float32 network too large for one workgroup's LDS -- MaximizableMixin._streamed's rule
+        lib = _lib.lib()
+        if ops.mlp_streamed(self.desc) & 2:
+            self._screen = (lib.bore_stream_sample_screen_topk, lib.bore_stream_screen_topk)
+            self._restarts = lib.bore_stream_lbfgsb_minimize
+        else:
+            self._screen = (lib.bore_sample_screen_topk, lib.bore_screen_topk)
+            self._restarts = lib.bore_lbfgsb_minimize
         self.transform = resolve(transform)
         assert self.transform.name is not None, "the replica engine runs on the device only: a named transform"
         self.gamma, self.epochs, self.batch_size = gamma, int(epochs), int(batch_size)
@@ -522,8 +539,9 @@ class ReplicaEngine:
             self.stats["fit_bytes"].append(Lg * self.epochs * (4 * N * (D + 1)
                                                                + steps * 24 * self.P))
             g.epochs_seen += self.epochs
+            sample_screen, screen = self._screen
             if self.select == "device":     # candidates recomputed in the screening kernel
-                _lib.check(lib.bore_sample_screen_topk(
+                _lib.check(sample_screen(
                     C.byref(self.desc), Lg, ptr(th), C.c_uint64(self.seed), int(self.loop_ids[g.a]),
                     g.draws, self.num_samples, self._lo_p, self._hi_p, R, ptr(g.x0), ptr(g.idx),
                     None, sp))
@@ -532,17 +550,15 @@ class ReplicaEngine:
                                                        int(self.loop_ids[g.a]), Lg, g.draws,
                                                        self.num_samples, D, self._lo_p, self._hi_p,
                                                        ptr(g.Xc), sp))
-                _lib.check(lib.bore_screen_topk(C.byref(self.desc), Lg, ptr(th), ptr(g.Xc),
-                                                self.num_samples, 0, R, ptr(g.x0), ptr(g.idx),
-                                                None, sp))
+                _lib.check(screen(C.byref(self.desc), Lg, ptr(th), ptr(g.Xc), self.num_samples, 0, R,
+                                  ptr(g.x0), ptr(g.idx), None, sp))
             g.draws += 1
             e2, e3 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e2.record()
-            _lib.check(lib.bore_lbfgsb_minimize(C.byref(self.desc), Lg, ptr(th),
-                                                _lib.TRANSFORM[tr.name], int(tr.negate),
-                                                ptr(g.x0), R, self._lo_p, self._hi_p,
-                                                C.byref(self._lopts), ptr(g.x), ptr(g.fun),
-                                                ptr(g.jac), ptr(g.info), sp))
+            _lib.check(self._restarts(C.byref(self.desc), Lg, ptr(th), _lib.TRANSFORM[tr.name],
+                                      int(tr.negate), ptr(g.x0), R, self._lo_p, self._hi_p,
+                                      C.byref(self._lopts), ptr(g.x), ptr(g.fun), ptr(g.jac),
+                                      ptr(g.info), sp))
             e3.record()
             self._ev2.append((e2, e3))
             if dev_sel:

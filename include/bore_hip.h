@@ -628,9 +628,15 @@ int bore_lstm_streamed(const bore_lstm_desc *desc, int T);
  * Workspace per call, stream-ordered: the rows kernels at most 64 MiB (or one 64-row tile per model), the fit
  * 2*64*sum(widths) + (batch_size > 64: P) floats per model, plus, with perm == NULL, the drawn shuffles
  * (n_models*epochs*N ints, at most 64 MiB: BORE_E_NEEDS_PERM beyond, as for N too long to rank in LDS).  One workgroup per model in the fit: a single
- * model leaves the rest of the device idle.  bore_screen_topk, bore_sample_screen_topk, bore_lbfgsb_minimize,
- * bore_svgd_optimize and the engine entry points keep the network in LDS and keep refusing such networks; screening,
- * restarts and SVGD have streamed entry points of their own (bore_stream_*, below).  Additive to ABI 12.
+ * model leaves the rest of the device idle.  bore_screen_topk, bore_sample_screen_topk, bore_lbfgsb_minimize and
+ * bore_svgd_optimize keep the network in LDS and keep refusing such networks; screening, restarts and SVGD have
+ * streamed entry points of their own (bore_stream_*, below).  The engine (bore_engine_create) takes such networks,
+ * and compute = BORE_COMPUTE_BF16 for the two wide shapes at batch_size 64, on its lock-step schedule
+ * (async_loops == 0): it asks bore_mlp_streamed(desc) & 2 once and calls bore_stream_sample_screen_topk and
+ * bore_stream_lbfgsb_minimize where it says so.  Its asynchronous schedule launches in batch mode (bore_set_batch),
+ * which the bfloat16 fit and every streamed entry point refuse: async_loops != 0 with such a descriptor is
+ * BORE_E_UNSUPPORTED at create, as is, on either schedule and before any HIP call, what no kernel takes (bfloat16
+ * outside the wide shapes or with another batch size, a float32 network of neither flavour).  Additive to ABI 12.
  * --------------------------------------------------------------------------------------------- */
 #define BORE_STREAM_MAX_UNITS 512
 #define BORE_STREAM_MAX_SAMPLES 16384 /* candidates per model the streamed screening ranks in one workgroup's LDS */
