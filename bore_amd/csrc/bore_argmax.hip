@@ -362,44 +362,42 @@ struct SampleSpec {
   const double *low, *high;
 };
 
-static int screen_build(const bore_mlp_desc *desc, int n_models, const float *theta,
-                        const double *X_init, const SampleSpec *spec, int64_t n_samples,
-                        int x_shared, int num_starts, double *x0, int32_t *idx, float *pred,
-                        ScreenArgs &a, size_t &lds_floats, int &shape_out) {
-  if (n_samples < 1 || n_samples > (1 << 20))
-    return fail(BORE_E_INVALID, "screen_topk: n_samples out of range");
-  if (num_starts < 1 || num_starts > n_samples)
-    return fail(BORE_E_INVALID, "screen_topk: need 1 <= num_starts <= n_samples");
+// What the screening entry points are asked for: their arguments up to `stream` (X_init or spec, the other null).
+struct ScreenRequest {
+  const bore_mlp_desc *desc; int n_models; const float *theta; const double *X_init; const SampleSpec *spec;
+  int64_t n_samples; int x_shared, num_starts; double *x0; int32_t *idx; float *pred;
+};
+
+// The forced choices of the acquisition launches (tests, A/B): BORE_LBFGSB_COOP_GRID (unset: 2^22),
+// _WAVES, _BIG, _QUEUE, _OCC2 and BORE_SCREEN_SPLIT (unset: -1).  Read once per call, by the entry point: the plans
+// below take them, the device's CU count and the batch mode as arguments and ask nothing of their surroundings.
+struct AcqKnobs { long long coop_grid = 1LL << 22, queue = -1; int waves = -1, big = -1, occ2 = -1, screen_split = -1; };
+static AcqKnobs acq_knobs() {
+  auto env = [](const char *name, long long unset) { return getenv(name) ? atoll(getenv(name)) : unset; };
+  return AcqKnobs{env("BORE_LBFGSB_COOP_GRID", 1LL << 22), env("BORE_LBFGSB_QUEUE", -1), (int)env("BORE_LBFGSB_WAVES", -1),
+                  (int)env("BORE_LBFGSB_BIG", -1), (int)env("BORE_LBFGSB_OCC2", -1), (int)env("BORE_SCREEN_SPLIT", -1)};
+}
+
+// A screening launch as planned from the request's sizes alone: no pointer is looked at.
+struct ScreenPlan {
+  ScreenArgs a;  // screen_plan: the layout, the LDS carve, n_pad and d_in; screen_build: the rest
+  size_t lds_floats;
+  int flavour, parts;  // parts: workgroups per model that predict before one selects (screen_body, MODE 1 / 2); 0: no split
+};
+
+static int screen_plan(const bore_mlp_desc *desc, int n_models, int64_t n_samples, int num_starts, bool pred,
+                       const AcqKnobs &knobs, int cus, bool batch, ScreenPlan &p) {
+  ScreenArgs &a = p.a;
+  if (n_samples < 1 || n_samples > (1 << 20)) return fail(BORE_E_INVALID, "screen_topk: n_samples out of range");
+  if (num_starts < 1 || num_starts > n_samples) return fail(BORE_E_INVALID, "screen_topk: need 1 <= num_starts <= n_samples");
   int n_pad = 1;
   while (n_pad < n_samples) n_pad <<= 1;
   const size_t key_floats = 2 * ((size_t)n_pad + 32) + 1 + BORE_LAYOUT_FLOATS + 4 + 4 * BORE_DIM_MAX + 4;
-  int rc = check_common(desc, n_models, 0, BORE_BATCH_MAX, true, key_floats, &a.L);
-  if (rc) return rc;
-  if (a.L.w[a.L.n_layers] != 1)
-    return fail(BORE_E_INVALID, "screen_topk: the last Dense layer must have 1 unit");
-  if (!theta || (!X_init && !spec) || !x0 || !idx) return fail(BORE_E_INVALID, "screen_topk: null pointer");
-  a.theta = theta; a.X = X_init; a.x0 = x0; a.idx = idx; a.pred = pred;
-  a.n_samples = n_samples; a.x_shared = x_shared; a.R = num_starts; a.n_pad = n_pad;
-  a.sampled = spec != nullptr;
-  a.seed = 0; a.model0 = 0; a.draw = 0;
-  a.ids = a.its = nullptr;
-  if (g_batch) {
-    if (!spec) return fail(BORE_E_INVALID, "screen_topk: batch mode needs the sampled form");
-    a.ids = g_batch->ids; a.its = g_batch->its;
-  }
-  if (spec) {
-    const int D = desc->input_dim;
-    if (D > BORE_DIM_MAX) return fail(BORE_E_UNSUPPORTED, "sample_screen_topk: D must be 1..%d", BORE_DIM_MAX);
-    if (!spec->low || !spec->high) return fail(BORE_E_INVALID, "sample_screen_topk: null bounds");
-    a.seed = spec->seed; a.model0 = spec->model_index0; a.draw = spec->draw_index;
-    for (int d = 0; d < D; ++d) {
-      a.box.lo[d] = spec->low[d];
-      a.box.hi[d] = spec->high[d];
-    }
-  }
+  if (const int rc = check_common(desc, n_models, 0, BORE_BATCH_MAX, true, key_floats, &a.L)) return rc;
+  if (a.L.w[a.L.n_layers] != 1) return fail(BORE_E_INVALID, "screen_topk: the last Dense layer must have 1 unit");
+  a.n_pad = n_pad; a.d_in = desc->input_dim;
   size_t off = a.L.P_lds;
-  a.d_in = desc->input_dim;
-  const int flav = bore_acq_flavour(desc, true);
+  const int flav = p.flavour = bore_acq_flavour(desc, true);  // (static flavours do not use the tile)
   const bool bf_img = desc->compute == BORE_COMPUTE_BF16 && bore_shape_is_wide(flav);
   // (a bfloat16 model: the fragment-order images of arg_bf16_mfma.h, activations in registers)
   if (bf_img) off = flav == 3 ? ArgBf16Plan<3>::floats : ArgBf16Plan<4>::floats;
@@ -411,76 +409,82 @@ static int screen_build(const bore_mlp_desc *desc, int n_models, const float *th
   a.total = (int)off;
   off = (off + 3) & ~(size_t)3;
   a.o_layout = (int)off; off += BORE_LAYOUT_FLOATS;
-  lds_floats = off;
-  shape_out = flav;  // (static flavours do not use the tile)
-  return 0;
-}
-
-static int screen_launch(const bore_mlp_desc *desc, int n_models, const float *theta,
-                         const double *X_init, const SampleSpec *spec, int64_t n_samples,
-                         int x_shared, int num_starts, double *x0, int32_t *idx, float *pred,
-                         void *stream) {
-  ScreenArgs a;
-  size_t off = 0;
-  int shape = 0;
-  int rc = screen_build(desc, n_models, theta, X_init, spec, n_samples, x_shared, num_starts, x0, idx,
-                        pred, a, off, shape);
-  if (rc) return rc;
+  p.lds_floats = off; p.parts = 0;
   // A few wide models, many candidates, and the caller gave a prediction buffer: the predictions run
   // on `parts` workgroups per model, then one workgroup per model selects (screen_body, MODE 1 / 2).
   // BORE_SCREEN_SPLIT = 0 / 1 forces either form.
-  if (pred && !g_batch && bore_shape_is_wide(shape)) {
-    const int forced = getenv("BORE_SCREEN_SPLIT") ? atoi(getenv("BORE_SCREEN_SPLIT")) : -1;
+  if (pred && !batch && bore_flavour_listed(WideFlavours{}, flav)) {
     const int n_blocks = (int)((n_samples + 15) >> 4);
-    int parts = device_cus() / (n_models > 0 ? n_models : 1);
+    int parts = cus / n_models;
     if (parts > n_blocks / 8) parts = n_blocks / 8;  // at least two row-blocks per wave
     if (parts > 64) parts = 64;
-    if (forced < 0 ? parts >= 4 : (forced != 0 && parts >= 2)) {
-      const bool bf = desc->compute == BORE_COMPUTE_BF16;
-      return bore_with_flavour(WideFlavours{}, shape, [&](auto S) {
-        auto launch = [&](auto B) {  // (both kernels' LDS limits raised before either is launched)
-          if ((rc = allow_lds(screen_topk_kernel<S(), B(), 1>, off * 4)) ||
-              (rc = allow_lds(screen_topk_kernel<S(), B(), 2>, off * 4)))
-            return rc;
-          hipLaunchKernelGGL((screen_topk_kernel<S(), B(), 1>), dim3(n_models, parts), dim3(BORE_THREADS), off * 4,
-                             (hipStream_t)stream, a);
-          hipLaunchKernelGGL((screen_topk_kernel<S(), B(), 2>), dim3(n_models), dim3(BORE_THREADS), off * 4,
-                             (hipStream_t)stream, a);
-          HIP_TRY(hipGetLastError());
-          return 0;
-        };
-        return !bf ? launch(std::false_type{}) : launch(std::true_type{});
-      });
-    }
+    if (knobs.screen_split < 0 ? parts >= 4 : (knobs.screen_split != 0 && parts >= 2)) p.parts = parts;
   }
-  if (desc->compute == BORE_COMPUTE_BF16) {
-    if (!bore_shape_is_wide(shape)) return fail(BORE_E_UNSUPPORTED, kBf16Shapes);
-    return bore_with_flavour(WideFlavours{}, shape, [&](auto S) {
-      return launch_lds(screen_topk_kernel<S(), true>, dim3(n_models), dim3(BORE_THREADS), off * 4, stream, a);
-    });
-  }
-  return bore_with_flavour(AcqFlavours{}, shape, [&](auto S) {
-    return launch_lds(screen_topk_kernel<S()>, dim3(n_models), dim3(BORE_THREADS), off * 4, stream, a);
-  });
+  return 0;
 }
 
-extern "C" int bore_screen_topk(const bore_mlp_desc *desc, int n_models, const float *theta,
-                                const double *X_init, int64_t n_samples, int x_shared,
-                                int num_starts, double *x0, int32_t *idx, float *pred,
+static int screen_build(const ScreenRequest &r, const AcqKnobs &knobs, ScreenPlan &p) {
+  ScreenArgs &a = p.a;
+  if (const int rc = screen_plan(r.desc, r.n_models, r.n_samples, r.num_starts, r.pred != nullptr, knobs, device_cus(),
+                                 g_batch != nullptr, p))
+    return rc;
+  if (!r.theta || (!r.X_init && !r.spec) || !r.x0 || !r.idx) return fail(BORE_E_INVALID, "screen_topk: null pointer");
+  a.theta = r.theta; a.X = r.X_init; a.x0 = r.x0; a.idx = r.idx; a.pred = r.pred;
+  a.n_samples = r.n_samples; a.x_shared = r.x_shared; a.R = r.num_starts;
+  a.sampled = r.spec != nullptr; a.seed = 0; a.model0 = 0; a.draw = 0; a.ids = a.its = nullptr;
+  if (g_batch) {
+    if (!r.spec) return fail(BORE_E_INVALID, "screen_topk: batch mode needs the sampled form");
+    a.ids = g_batch->ids; a.its = g_batch->its;
+  }
+  if (r.spec) {
+    const int D = r.desc->input_dim;
+    if (D > BORE_DIM_MAX) return fail(BORE_E_UNSUPPORTED, "sample_screen_topk: D must be 1..%d", BORE_DIM_MAX);
+    if (!r.spec->low || !r.spec->high) return fail(BORE_E_INVALID, "sample_screen_topk: null bounds");
+    a.seed = r.spec->seed; a.model0 = r.spec->model_index0; a.draw = r.spec->draw_index;
+    for (int d = 0; d < D; ++d) { a.box.lo[d] = r.spec->low[d]; a.box.hi[d] = r.spec->high[d]; }
+  }
+  return 0;
+}
+
+static int screen_launch(const ScreenRequest &r, void *stream) {
+  ScreenPlan p;
+  int rc = screen_build(r, acq_knobs(), p);
+  if (rc) return rc;
+  const size_t lds = p.lds_floats * 4;
+  const bool bf = r.desc->compute == BORE_COMPUTE_BF16;
+  const dim3 block(BORE_THREADS);
+  if (p.parts)
+    return bore_with_flavour(WideFlavours{}, p.flavour, [&](auto S) {
+      auto launch = [&](auto B) {  // (both kernels' LDS limits raised before either is launched)
+        if ((rc = allow_lds(screen_topk_kernel<S(), B(), 1>, lds)) || (rc = allow_lds(screen_topk_kernel<S(), B(), 2>, lds)))
+          return rc;
+        hipLaunchKernelGGL((screen_topk_kernel<S(), B(), 1>), dim3(r.n_models, p.parts), block, lds, (hipStream_t)stream, p.a);
+        hipLaunchKernelGGL((screen_topk_kernel<S(), B(), 2>), dim3(r.n_models), block, lds, (hipStream_t)stream, p.a);
+        HIP_TRY(hipGetLastError());
+        return 0;
+      };
+      return !bf ? launch(std::false_type{}) : launch(std::true_type{});
+    });
+  if (bf && !bore_shape_is_wide(p.flavour)) return fail(BORE_E_UNSUPPORTED, kBf16Shapes);
+  auto launch = [&](auto kernel) { return launch_lds(kernel, dim3(r.n_models), block, lds, stream, p.a); };
+  if (bf) return bore_with_flavour(WideFlavours{}, p.flavour, [&](auto S) { return launch(screen_topk_kernel<S(), true>); });
+  return bore_with_flavour(AcqFlavours{}, p.flavour, [&](auto S) { return launch(screen_topk_kernel<S()>); });
+}
+
+extern "C" int bore_screen_topk(const bore_mlp_desc *desc, int n_models, const float *theta, const double *X_init,
+                                int64_t n_samples, int x_shared, int num_starts, double *x0, int32_t *idx, float *pred,
                                 void *stream) {
   if (!X_init) return fail(BORE_E_INVALID, "screen_topk: null pointer");
-  return screen_launch(desc, n_models, theta, X_init, nullptr, n_samples, x_shared, num_starts, x0,
-                       idx, pred, stream);
+  return screen_launch(ScreenRequest{desc, n_models, theta, X_init, nullptr, n_samples, x_shared, num_starts, x0, idx, pred},
+                       stream);
 }
 
-extern "C" int bore_sample_screen_topk(const bore_mlp_desc *desc, int n_models, const float *theta,
-                                       uint64_t seed, int64_t model_index0, int64_t draw_index,
-                                       int64_t n_samples, const double *low, const double *high,
-                                       int num_starts, double *x0, int32_t *idx, float *pred,
+extern "C" int bore_sample_screen_topk(const bore_mlp_desc *desc, int n_models, const float *theta, uint64_t seed,
+                                       int64_t model_index0, int64_t draw_index, int64_t n_samples, const double *low,
+                                       const double *high, int num_starts, double *x0, int32_t *idx, float *pred,
                                        void *stream) {
   const SampleSpec spec{seed, model_index0, draw_index, low, high};
-  return screen_launch(desc, n_models, theta, nullptr, &spec, n_samples, 0, num_starts, x0, idx,
-                       pred, stream);
+  return screen_launch(ScreenRequest{desc, n_models, theta, nullptr, &spec, n_samples, 0, num_starts, x0, idx, pred}, stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -627,7 +631,7 @@ __device__ __forceinline__ void lbfgsb_body(const LbfgsbArgs &a, const long long
   int *qnext = reinterpret_cast<int *>(smem + a.o_queue);
   if (queue && tid == 0) *qnext = NW;  // (the first NW problems go to the waves in order)
   // (the pooled matrices are compiled into the one kernel whose launches use them: the eight-wave kernel of
-  // the 128-wide shape; lbfgsb_build decides per launch)
+  // the 128-wide shape; lbfgsb_plan decides per launch)
   constexpr bool BIG_OK = ALWAYS_COOP && SHAPE == 4;
   const bool use_big = BIG_OK && a.big != nullptr;
   if (use_big && tid == 0) {
@@ -859,7 +863,7 @@ __device__ __forceinline__ void lbfgsb_body(const LbfgsbArgs &a, const long long
   }
   if constexpr (ALWAYS_COOP) {
     // (cannot happen: these kernels' launches give a wave one problem at a time -- engine_create,
-    // lbfgsb_build.  If a caller ever breaks that, the problems are REPORTED, unoptimised, with status 2
+    // lbfgsb_plan.  If a caller ever breaks that, the problems are REPORTED, unoptimised, with status 2
     // below -- every flag is published, no host waits -- instead of being dropped silently.)
   } else {
   for (int round = 0; !direct && round < a.max_rounds; ++round) {
@@ -1165,38 +1169,47 @@ static int lbfgsb_convert(int D, int transform, int num_starts, const double *lb
   return 0;
 }
 
-static int lbfgsb_check_args(const bore_mlp_desc *desc, int n_models, const float *theta, int transform,
-                             const double *x0, int num_starts, const double *lb, const double *ub,
-                             const bore_lbfgsb_opts *opts, const double *x, const double *fun, const double *jac,
-                             const int32_t *info, BoxArgs &box, int *nbd, lbfgsb::Options &opt) {
-  if (!desc || !theta || !x0 || !lb || !ub || !opts || !x || !fun || !jac || !info)
+// The optimiser's own limit of rounds for one problem (every round serves one request of it).
+static inline long long lbfgsb_round_cap(const bore_lbfgsb_opts *opts) { return (long long)opts->maxfun + opts->maxls + 64; }
+
+// What the restart entry points are asked for: their arguments up to `stream`, under their names in include/bore_hip.h.
+struct LbfgsbRequest {
+  const bore_mlp_desc *desc; int n_models; const float *theta; int transform, negate; const double *x0; int num_starts;
+  const double *lb, *ub; const bore_lbfgsb_opts *opts; double *x, *fun, *jac; int32_t *info;
+};
+
+static int lbfgsb_check_args(const LbfgsbRequest &r, BoxArgs &box, int *nbd, lbfgsb::Options &opt) {
+  if (!r.desc || !r.theta || !r.x0 || !r.lb || !r.ub || !r.opts || !r.x || !r.fun || !r.jac || !r.info)
     return fail(BORE_E_INVALID, "lbfgsb_minimize: null pointer");
-  if (n_models < 1) return fail(BORE_E_INVALID, "n_models must be >= 1 (got %d)", n_models);
-  const int D = desc->input_dim;
-  if (D < 1 || D > BORE_DIM_MAX)
-    return fail(BORE_E_UNSUPPORTED, "lbfgsb_minimize: input_dim must be 1..%d", BORE_DIM_MAX);
-  return lbfgsb_convert(D, transform, num_starts, lb, ub, opts, box, nbd, opt);
+  if (r.n_models < 1) return fail(BORE_E_INVALID, "n_models must be >= 1 (got %d)", r.n_models);
+  const int D = r.desc->input_dim;
+  if (D < 1 || D > BORE_DIM_MAX) return fail(BORE_E_UNSUPPORTED, "lbfgsb_minimize: input_dim must be 1..%d", BORE_DIM_MAX);
+  return lbfgsb_convert(D, r.transform, r.num_starts, r.lb, r.ub, r.opts, box, nbd, opt);
 }
 
-static int lbfgsb_build(const bore_mlp_desc *desc, int n_models, const float *theta,
-                        int transform, int negate, const double *x0, int num_starts,
-                        const double *lb, const double *ub, const bore_lbfgsb_opts *opts, double *x,
-                        double *fun, double *jac, int32_t *info, LbfgsbArgs &a, size_t &lds_floats,
-                        int &flavour_out, int &blocks_out, int *waves_out = nullptr) {
-  if (const int rc = lbfgsb_check_args(desc, n_models, theta, transform, x0, num_starts, lb, ub, opts, x, fun, jac, info,
-                                       a.box, a.nbd, a.opt))
-    return rc;
-  const int D = desc->input_dim, m = a.opt.m;
-  // per-problem LDS block: fp64 workspace | int workspace (8-byte aligned); the scalar
-  // State lives in registers
-  const size_t state_f = 0;
-  size_t dw_f = 2 * (size_t)lbfgsb::dwork_size(D, m);
-  const size_t iw_f = ((size_t)lbfgsb::iwork_size(D) + 3) & ~(size_t)3;
-  a.o_state = 0;
-  a.o_dw = (int)state_f;
-  a.o_iw = (int)(state_f + dw_f);
-  a.prob_floats = (int)(state_f + dw_f + iw_f);
-  a.big = nullptr; a.big_locks = nullptr; a.big_wave = 0;
+// The restart kernels (lbfgsb_kernel*): four waves, two such workgroups per CU, and the many-wave ones.
+enum class RestartKernel { W4_F32, W4_BF16, OCC2, W8_F32, W8_BF16, W12 };
+
+// A restart launch as planned from the request's sizes alone: no pointer is looked at, nothing is allocated.
+struct LbfgsbPlan {
+  LbfgsbArgs a;  // lbfgsb_plan: the layout, the LDS carve, PB, queue and d_in; lbfgsb_build: the rest
+  size_t lds_floats;
+  int flavour, slots, waves, blocks;  // workspaces (= waves with a problem), waves per workgroup, grid.y
+  RestartKernel kernel;  // (of bore_lbfgsb_minimize's launch; the fused kernel runs lbfgsb_body as one of its phases)
+  size_t pool_doubles;  // per slot of the device pool (big_pool) that holds the optimiser's matrices; 0: none
+};
+
+// `batch`: the batch mode the launch runs in (bore_set_batch; nullptr: none); `many_waves`: the caller can launch the
+// eight- and twelve-wave kernels (the fused kernel, which runs the restarts as one of its phases, cannot).
+static int lbfgsb_plan(const bore_mlp_desc *desc, int n_models, int num_starts, int m, const AcqKnobs &knobs, int cus,
+                       const bore_batch *batch, bool many_waves, LbfgsbPlan &p) {
+  LbfgsbArgs &a = p.a;
+  const int D = a.d_in = desc->input_dim;
+  const int flavour = p.flavour = bore_acq_flavour(desc, true);
+  const bool bf16_model = desc->compute == BORE_COMPUTE_BF16;
+  // which many-wave kernel the flavour has: asked of the lists the launch below instantiates them for
+  const bool narrow = bore_flavour_listed(NarrowWavesFlavours{}, flavour), has_w12 = narrow && !bf16_model;
+  const bool has_w8 = bf16_model ? bore_flavour_listed(WideFlavours{}, flavour) : bore_flavour_listed(FlavourList<3>{}, flavour);
   // largest number of problems per workgroup whose state fits beside theta and the tile
   // (tile rows: one 16-row block per wave that has a problem)
   int PB = num_starts < BORE_BATCH_MAX ? num_starts : BORE_BATCH_MAX;
@@ -1206,11 +1219,7 @@ static int lbfgsb_build(const bore_mlp_desc *desc, int n_models, const float *th
   // the one-problem-per-wave mapping is 2.0x / 1.5x faster than 64 problems per workgroup there as
   // well: lanes that each run their own state machine diverge; profiles/r2/lbfgsb_mapping.txt.  The
   // lane-per-problem mapping is kept for grids beyond 4 M workgroups and for BORE_LBFGSB_COOP_GRID.)
-  const long long coop_grid_max =
-      getenv("BORE_LBFGSB_COOP_GRID") ? atoll(getenv("BORE_LBFGSB_COOP_GRID")) : (1LL << 22);
-  if (PB > 4 && !g_batch && (long long)n_models * ((num_starts + 3) / 4) <= coop_grid_max) PB = 4;
-  const int flavour = bore_acq_flavour(desc, true);
-  a.d_in = D;
+  if (PB > 4 && !batch && (long long)n_models * ((num_starts + 3) / 4) <= knobs.coop_grid) PB = 4;
   // More workgroups than CUs, static shape: ONE workgroup per CU with a problem per wave and as many waves as
   // workspaces fit beside the weights, up to the kernel's launch bound -- 8 for the wide shapes (lbfgsb_kernel_w8),
   // 12 for the narrow ones (lbfgsb_kernel_w12, the same body at 168 registers).  The restart kernels are chains of
@@ -1218,86 +1227,80 @@ static int lbfgsb_build(const bore_mlp_desc *desc, int n_models, const float *th
   // waves of 16->64-64-64-1 at 168 registers (154 spilled) measured no faster than eight at 256, sixteen of 6->32-32-1
   // at 128 (90 spilled) slower than twelve (profiles/r6/ab_log.txt).  BORE_LBFGSB_WAVES = 4 keeps the four-wave
   // kernels, = 8 / 12 forces the many-wave kernel with at most that many waves (tests, A/B).
-  const int waves_env = getenv("BORE_LBFGSB_WAVES") ? atoi(getenv("BORE_LBFGSB_WAVES")) : -1;
-  const bool bf16_model = desc->compute == BORE_COMPUTE_BF16;
   int wmax = 4;  // waves (= problems at a time) per workgroup of this launch's kernel
-  if (waves_out && !g_batch && PB == 4) {
+  if (many_waves && !batch && PB == 4) {
     int bound = 4;
-    if ((flavour == 3 || (flavour == 4 && bf16_model)) && num_starts >= 8) bound = 8;
-    if ((flavour == 2 || flavour == 5) && !bf16_model && num_starts >= 12) bound = 12;
-    if (waves_env >= 4) wmax = bound < waves_env ? bound : waves_env;
-    else if ((long long)n_models * ((num_starts + 3) / 4) > device_cus()) wmax = bound;
+    if (has_w8 && num_starts >= 8) bound = 8;
+    if (has_w12 && num_starts >= 12) bound = 12;
+    if (knobs.waves >= 4) wmax = bound < knobs.waves ? bound : knobs.waves;
+    else if ((long long)n_models * ((num_starts + 3) / 4) > cus) wmax = bound;
     if (wmax > num_starts) wmax = num_starts;
     if (wmax < 8) wmax = 4;
     PB = wmax;
   }
-  const bool w8 = wmax > 4 && (flavour == 3 || flavour == 4);
   const int shape = flavour > 0 ? flavour : 0;  // constexpr-layout kernels assume a 64-row tile
-  size_t off = 0;
-  for (;; --PB) {
-    if (PB < 1)
-      return fail(BORE_E_UNSUPPORTED, "lbfgsb_minimize: one problem's state does not fit in LDS beside the network; %s",
-                  kStreamedElsewhere);
+  // The carve for pb problems per workgroup (`pooled`: the optimiser's two 2m x 2m matrices in the device pool, not in
+  // the problem's block); returns the floats it takes, 0 for a descriptor that has no layout.
+  // per-problem LDS block: fp64 workspace | int workspace (8-byte aligned); the scalar State lives in registers
+  const size_t iw_f = ((size_t)lbfgsb::iwork_size(D) + 3) & ~(size_t)3;
+  a.o_state = a.o_dw = 0;
+  auto carve = [&](int pb, bool pooled) -> size_t {
+    const size_t dw_f = 2 * (size_t)lbfgsb::dwork_size(D, m, pooled);
+    a.o_iw = (int)dw_f;
+    a.prob_floats = (int)(dw_f + iw_f);
     // static flavours keep the row-blocks in registers; their tile region only stages the
     // points (A_0) and gradients (D_0) of waves that run several problems: 2 x 64 rows
-    const int rows = shape ? 16 : 16 * (PB < 4 ? PB : 4);
-    if (bore_make_layout(desc, 2, rows, &a.L)) return fail(BORE_E_INVALID, "bad bore_mlp_desc");
+    const int rows = shape ? 16 : 16 * (pb < 4 ? pb : 4);
+    if (bore_make_layout(desc, 2, rows, &a.L)) return 0;
     // (a bfloat16 image holds 2-byte elements at the float image's indices: half its bytes.  Round 2
     // reserved the float size, which left BASELINE config 5 -- 128-128-1 -- room for three problems per
     // workgroup and kept it out of the eight-wave kernel; with the true size six fit.)
-    off = desc->compute == BORE_COMPUTE_BF16 ? ((size_t)a.L.P_lds + 1) / 2 : (size_t)a.L.P_lds;
+    size_t off = bf16_model ? ((size_t)a.L.P_lds + 1) / 2 : (size_t)a.L.P_lds;
     // (round 4: wide static shapes in bfloat16 hold the fragment-order images of arg_bf16_mfma.h -- forward
     // and backward operands of the bf16 matrix instructions, about twice the plain bfloat16 image)
-    if (desc->compute == BORE_COMPUTE_BF16 && bore_shape_is_wide(flavour))
-      off = flavour == 3 ? ArgBf16Plan<3>::floats : ArgBf16Plan<4>::floats;
+    if (bf16_model && bore_shape_is_wide(flavour)) off = flavour == 3 ? ArgBf16Plan<3>::floats : ArgBf16Plan<4>::floats;
     off = (off + 3) & ~(size_t)3;
     a.o_tile = (int)off;
     // (one problem per wave -- up to 4 problems, 8 in the eight-wave kernel, 16 in batch mode -- reads
     // its point straight from the optimiser's vector: no staging region at all)
-    const bool per_wave = PB <= wmax || (g_batch && PB <= 16);
+    const bool per_wave = pb <= wmax || (batch && pb <= 16);
     off += shape ? (per_wave ? 0 : 2 * (size_t)BORE_BATCH_MAX * a.L.lda[0]) : (size_t)a.L.tile_floats;
     a.o_vals = (int)off; off += BORE_BATCH_MAX;
     off = (off + 3) & ~(size_t)3;  // 16-byte boundary for the fp64 regions
     a.o_box = (int)off; off += 4 * (size_t)D + (((size_t)D + 3) & ~(size_t)3) + (D & 1 ? 2 : 0);
     off = (off + 3) & ~(size_t)3;
-    a.o_prob = (int)off; off += (size_t)a.prob_floats * PB;
+    a.o_prob = (int)off; off += (size_t)a.prob_floats * pb;
     off = (off + 3) & ~(size_t)3;
     a.o_res = (int)off;  // batch mode: [max(R, 4)][D + 3] fp64 + the finished-problem counter
     // (+ the finished-problem counter and the per-problem counts of executed evaluations)
-    off += g_batch ? 2 * (size_t)(num_starts > 4 ? num_starts : 4) * ((size_t)D + 3) + 4 + 16 : 0;
+    off += batch ? 2 * (size_t)(num_starts > 4 ? num_starts : 4) * ((size_t)D + 3) + 4 + 16 : 0;
     a.o_queue = (int)off; off += 4;  // (the queue's next-problem counter)
     a.total = (int)off;
     off = (off + 3) & ~(size_t)3;
     a.o_layout = (int)off; off += BORE_LAYOUT_FLOATS;
+    return off;
+  };
+  size_t off = 0;
+  for (;; --PB) {
+    if (PB < 1)
+      return fail(BORE_E_UNSUPPORTED, "lbfgsb_minimize: one problem's state does not fit in LDS beside the network; %s",
+                  kStreamedElsewhere);
+    if (!(off = carve(PB, false))) return fail(BORE_E_INVALID, "bad bore_mlp_desc");
     if (off * 4 <= BORE_LDS_BYTES) break;
   }
   // The eight-wave kernel with fewer than eight problems beside the weights (32->128-128-1: six): with the
   // optimiser's two 2m x 2m matrices in a slot of the device pool instead of in LDS eight fit (the matrices
   // are touched by the subspace minimisation only -- once in a hundred evaluations of BASELINE config 5).
   // BORE_LBFGSB_BIG = 0 / 1 forces the choice (tests, A/B).
-  if (w8 && !g_batch && flavour == 4) {  // (lbfgsb_body: BIG_OK)
-    const int forced = getenv("BORE_LBFGSB_BIG") ? atoi(getenv("BORE_LBFGSB_BIG")) : -1;
+  p.pool_doubles = 0;
+  if (wmax > 4 && flavour == 4) {  // (lbfgsb_body: BIG_OK)
     const size_t small_f = 2 * (size_t)lbfgsb::dwork_size(D, m, true) + iw_f;
     const size_t fixed = off - (size_t)a.prob_floats * PB;   // everything but the problems (floats)
     int PB2 = (int)((BORE_LDS_BYTES / 4 - fixed) / small_f);
     if (PB2 > 8) PB2 = 8;
-    if (PB2 >= 1 && (forced < 0 ? PB2 > PB : forced != 0)) {
-      BigPool pool;
-      const int rcp = big_pool(8 * (size_t)lbfgsb::big_size(m), &pool);
-      if (rcp) return rcp;
-      a.big = pool.buf; a.big_locks = pool.locks; a.big_wave = (int)(pool.per_slot / 8);
-      // re-carve with the smaller problem blocks (same order of regions as in the loop above)
-      PB = PB2;
-      dw_f = 2 * (size_t)lbfgsb::dwork_size(D, m, true);
-      a.o_iw = (int)(state_f + dw_f);
-      a.prob_floats = (int)(state_f + dw_f + iw_f);
-      off = (size_t)a.o_prob + (size_t)a.prob_floats * PB;
-      off = (off + 3) & ~(size_t)3;
-      a.o_res = (int)off;
-      a.o_queue = (int)off; off += 4;
-      a.total = (int)off;
-      off = (off + 3) & ~(size_t)3;
-      a.o_layout = (int)off; off += BORE_LAYOUT_FLOATS;
+    if (PB2 >= 1 && (knobs.big < 0 ? PB2 > PB : knobs.big != 0)) {
+      p.pool_doubles = 8 * (size_t)lbfgsb::big_size(m);
+      off = carve(PB = PB2, true);
       if (off * 4 > BORE_LDS_BYTES) return fail(BORE_E_UNSUPPORTED, "lbfgsb_minimize: LDS carve with the pooled matrices");
     }
   }
@@ -1305,16 +1308,14 @@ static int lbfgsb_build(const bore_mlp_desc *desc, int n_models, const float *th
   // share of the restarts from a queue (lbfgsb_body).  About four workgroups per CU over the launch;
   // BORE_LBFGSB_QUEUE = 0 keeps one workgroup per PB restarts, = n > 0 asks for n workgroups in all
   // (A/B, tests).
-  const int slots = PB;  // workspaces = waves with a problem
+  const int slots = p.slots = PB;  // workspaces = waves with a problem
   a.queue = 0;
-  const long long q_env = getenv("BORE_LBFGSB_QUEUE") ? atoll(getenv("BORE_LBFGSB_QUEUE")) : -1;
-  if (!g_batch && PB <= wmax && num_starts > PB && q_env != 0) {
+  if (!batch && PB <= wmax && num_starts > PB && knobs.queue != 0) {
     // (the 32-32-1 flavour stages 6 KB of weights and runs two workgroups per CU: finer shares -- 32 per CU
     // over the launch -- measured best there, profiles/r4/ab_log.txt; the wide flavours stage 40 - 50 KB)
     // (round 6, tools/ab_restarts.py on fixed inputs, profiles/r6/ab_queue_shares.txt: 4 per CU is the best or within
     // 0.2 % of it for the twelve- / eight-wave float32 kernels; 32->128-128-1 in bfloat16 gains 4 % from 8 per CU)
-    const long long want = q_env > 0 ? q_env
-                                     : ((flavour == 2 || flavour == 5) && wmax == 4 ? 32LL : (flavour == 4 ? 8LL : 4LL)) * device_cus();
+    const long long want = knobs.queue > 0 ? knobs.queue : (narrow && wmax == 4 ? 32LL : (flavour == 4 ? 8LL : 4LL)) * cus;
     long long per_model = (want + n_models - 1) / n_models;
     const long long most = (num_starts + slots - 1) / slots;
     if (per_model > most) per_model = most;
@@ -1323,89 +1324,84 @@ static int lbfgsb_build(const bore_mlp_desc *desc, int n_models, const float *th
     a.queue = PB > slots;
   }
   a.PB = PB;
-  if (waves_out) *waves_out = wmax > 4 && slots > 4 ? slots : 4;
-  if (a.L.w[a.L.n_layers] != 1)
-    return fail(BORE_E_INVALID, "lbfgsb_minimize: the last Dense layer must have 1 unit");
-  a.theta = theta; a.x0 = x0; a.x = x; a.fun = fun; a.jac = jac; a.info = info;
-  a.R = num_starts; a.transform = transform; a.sign = negate ? -1.f : 1.f;
-  a.ids = a.its = nullptr; a.n_init = a.dedup = 0; a.cap = 0;
-  a.X_seen = nullptr; a.result = nullptr; a.flag = nullptr; a.stamps = nullptr;
-  a.flag_by_store = device_host_atomics() ? 0 : 1;
-  if (g_batch) {
+  p.waves = wmax > 4 && slots > 4 ? slots : 4;
+  p.lds_floats = off;
+  if (a.L.w[a.L.n_layers] != 1) return fail(BORE_E_INVALID, "lbfgsb_minimize: the last Dense layer must have 1 unit");
+  if (batch) {
     if (num_starts > 16 || PB < num_starts)
       return fail(BORE_E_UNSUPPORTED, "lbfgsb_minimize: batch mode needs num_starts <= 16 in one workgroup");
-    if (!g_batch->ids || !g_batch->its || !g_batch->result || !g_batch->flag ||
-        (g_batch->deduplicate && !g_batch->X_seen))
+    if (!batch->ids || !batch->its || !batch->result || !batch->flag || (batch->deduplicate && !batch->X_seen))
       return fail(BORE_E_INVALID, "lbfgsb_minimize: incomplete bore_batch");
-    a.ids = g_batch->ids; a.its = g_batch->its; a.n_init = g_batch->n_init;
-    a.dedup = g_batch->deduplicate; a.cap = g_batch->cap; a.X_seen = g_batch->X_seen;
-    a.result = g_batch->result; a.flag = g_batch->flag;
   }
-  long long cap = (long long)opts->maxfun + opts->maxls + 64;
-  a.max_rounds = (int)(cap > (1 << 24) ? (1 << 24) : cap);
-  const int blocks = (num_starts + PB - 1) / PB;
+  const int blocks = p.blocks = (num_starts + PB - 1) / PB;
   if (blocks > 65535) return fail(BORE_E_UNSUPPORTED, "lbfgsb_minimize: too many restarts");
-  lds_floats = off;
-  flavour_out = flavour;
-  blocks_out = blocks;
-  return 0;
-}
-
-extern "C" int bore_lbfgsb_minimize(const bore_mlp_desc *desc, int n_models, const float *theta,
-                                    int transform, int negate, const double *x0, int num_starts,
-                                    const double *lb, const double *ub,
-                                    const bore_lbfgsb_opts *opts, double *x, double *fun,
-                                    double *jac, int32_t *info, void *stream) {
-  LbfgsbArgs a;
-  size_t off = 0;
-  int flavour = 0, blocks = 0, waves = 4;
-  int rc = lbfgsb_build(desc, n_models, theta, transform, negate, x0, num_starts, lb, ub, opts, x, fun,
-                        jac, info, a, off, flavour, blocks, &waves);
-  if (rc) return rc;
-  if (waves > 4) {  // (wide static shape, more workgroups than CUs: see lbfgsb_build)
-    const bool bf = desc->compute == BORE_COMPUTE_BF16;
+  // Which kernel.  (the many-wave kernel whose launch bound covers the waves: a launch of fewer waves is fine)
+  if (p.waves > 4) {  // (static shape, more workgroups than CUs: see wmax above)
     if (!bore_flavour_on(flavour)) return fail(BORE_E_UNSUPPORTED, BORE_FLAVOUR_LEFT_OUT);
-    if (!(flavour == 3 || (flavour == 4 && bf) || ((flavour == 2 || flavour == 5) && !bf)))
-      return fail(BORE_E_UNSUPPORTED, "lbfgsb_minimize: no many-wave kernel for this flavour");
-    // (the kernel whose launch bound covers the waves: a launch of fewer waves than the bound is fine)
-    const dim3 grid(n_models, blocks), block(64 * waves);
-    if (!bore_shape_is_wide(flavour))
-      return bore_with_flavour(NarrowWavesFlavours{}, flavour, [&](auto S) {
-        return launch_lds(lbfgsb_kernel_w12<S(), false>, grid, block, off * 4, stream, a);
-      });
-    if (!bf)  // (float32: 16->64-64-64-1 alone has an eight-wave kernel -- 32->128-128-1 was refused above)
-      return bore_with_flavour(FlavourList<3>{}, flavour, [&](auto S) {
-        return launch_lds(lbfgsb_kernel_w8<S(), false>, grid, block, off * 4, stream, a);
-      });
-    return bore_with_flavour(WideFlavours{}, flavour, [&](auto S) {
-      return launch_lds(lbfgsb_kernel_w8<S(), true>, grid, block, off * 4, stream, a);
-    });
-  }
-  if (desc->compute == BORE_COMPUTE_BF16) {
+    if (!has_w8 && !has_w12) return fail(BORE_E_UNSUPPORTED, "lbfgsb_minimize: no many-wave kernel for this flavour");
+    p.kernel = has_w12 ? RestartKernel::W12 : bf16_model ? RestartKernel::W8_BF16 : RestartKernel::W8_F32;
+  } else if (bf16_model) {
     if (!bore_shape_is_wide(flavour)) return fail(BORE_E_UNSUPPORTED, kBf16Shapes);
-    return bore_with_flavour(WideFlavours{}, flavour, [&](auto S) {
-      return launch_lds(lbfgsb_kernel<S(), true>, dim3(n_models, blocks), dim3(BORE_THREADS), off * 4, stream, a);
-    });
-  }
-  {
+    p.kernel = RestartKernel::W4_BF16;
+  } else {
     // More workgroups than CUs (many loops x many restarts): the 32-32-1 flavour, whose workgroup
     // needs 48 KB of LDS, runs two workgroups per CU (256 registers per lane, operands re-requested
     // per evaluation, 132 B of scratch) -- restarts of BASELINE config 2 with 256 loops 78.7 -> 43.1 ms,
     // same bits.  A single loop's launch (64 workgroups) keeps the one-per-CU kernel: it finishes a
     // problem sooner.  BORE_LBFGSB_OCC2 = 0 / 1 forces either (tests, measurements).
-    const int forced = getenv("BORE_LBFGSB_OCC2") ? atoi(getenv("BORE_LBFGSB_OCC2")) : -1;
-    const bool many = (long long)n_models * blocks > device_cus();
     // (one problem per wave only: the kernel does not carry the lane-per-problem loop)
-    // (launches with many workgroups of a narrow shape take the twelve-wave kernel above first: lbfgsb_build)
-    if ((flavour == 2 || flavour == 5) && (a.PB <= 4 || a.queue) && off * 4 <= BORE_LDS_BYTES / 2 &&
-        (forced < 0 ? many : forced != 0))  // (5: the plugin's default network: 5 restarts per loop, many loops)
-      return bore_with_flavour(NarrowWavesFlavours{}, flavour, [&](auto S) {
-        return launch_lds(lbfgsb_kernel_occ2<S()>, dim3(n_models, blocks), dim3(BORE_THREADS), off * 4, stream, a);
-      });
+    // (launches with many workgroups of a narrow shape take the twelve-wave kernel first: wmax above)
+    const bool many = (long long)n_models * blocks > cus;
+    const bool occ2 = narrow && (PB <= 4 || a.queue) && off * 4 <= BORE_LDS_BYTES / 2 &&
+                      (knobs.occ2 < 0 ? many : knobs.occ2 != 0);  // (5: the plugin's default network: 5 restarts per loop, many loops)
+    p.kernel = occ2 ? RestartKernel::OCC2 : RestartKernel::W4_F32;
   }
-  return bore_with_flavour(AcqFlavours{}, flavour, [&](auto S) {
-    return launch_lds(lbfgsb_kernel<S()>, dim3(n_models, blocks), dim3(BORE_THREADS), off * 4, stream, a);
-  });
+  return 0;
+}
+
+static int lbfgsb_build(const LbfgsbRequest &r, const AcqKnobs &knobs, bool many_waves, LbfgsbPlan &p) {
+  LbfgsbArgs &a = p.a;
+  int rc = lbfgsb_check_args(r, a.box, a.nbd, a.opt);
+  if (rc || (rc = lbfgsb_plan(r.desc, r.n_models, r.num_starts, a.opt.m, knobs, device_cus(), g_batch, many_waves, p)))
+    return rc;
+  BigPool pool;  // (nothing, unless the plan wants one)
+  if (p.pool_doubles && (rc = big_pool(p.pool_doubles, &pool))) return rc;
+  a.big = pool.buf; a.big_locks = pool.locks; a.big_wave = (int)(pool.per_slot / 8);
+  a.theta = r.theta; a.x0 = r.x0; a.x = r.x; a.fun = r.fun; a.jac = r.jac; a.info = r.info;
+  a.R = r.num_starts; a.transform = r.transform; a.sign = r.negate ? -1.f : 1.f;
+  const bore_batch none{}, &b = g_batch ? *g_batch : none;  // (no batch mode: nulls and zeros)
+  a.ids = b.ids; a.its = b.its; a.n_init = b.n_init; a.dedup = b.deduplicate; a.cap = b.cap; a.X_seen = b.X_seen;
+  a.result = b.result; a.flag = b.flag; a.stamps = nullptr;
+  a.flag_by_store = device_host_atomics() ? 0 : 1;
+  const long long cap = lbfgsb_round_cap(r.opts);
+  a.max_rounds = (int)(cap > (1 << 24) ? (1 << 24) : cap);
+  return 0;
+}
+
+extern "C" int bore_lbfgsb_minimize(const bore_mlp_desc *desc, int n_models, const float *theta, int transform, int negate,
+                                    const double *x0, int num_starts, const double *lb, const double *ub,
+                                    const bore_lbfgsb_opts *opts, double *x, double *fun, double *jac, int32_t *info,
+                                    void *stream) {
+  LbfgsbPlan p;
+  if (const int rc = lbfgsb_build(LbfgsbRequest{desc, n_models, theta, transform, negate, x0, num_starts, lb, ub, opts, x,
+                                                fun, jac, info}, acq_knobs(), true, p))
+    return rc;
+  const dim3 grid(n_models, p.blocks), block(64 * p.waves);
+  auto launch = [&](auto kernel) { return launch_lds(kernel, grid, block, p.lds_floats * 4, stream, p.a); };
+  switch (p.kernel) {
+    case RestartKernel::W12:
+      return bore_with_flavour(NarrowWavesFlavours{}, p.flavour, [&](auto S) { return launch(lbfgsb_kernel_w12<S(), false>); });
+    case RestartKernel::W8_F32:  // (float32: 16->64-64-64-1 alone has an eight-wave kernel)
+      return bore_with_flavour(FlavourList<3>{}, p.flavour, [&](auto S) { return launch(lbfgsb_kernel_w8<S(), false>); });
+    case RestartKernel::W8_BF16:
+      return bore_with_flavour(WideFlavours{}, p.flavour, [&](auto S) { return launch(lbfgsb_kernel_w8<S(), true>); });
+    case RestartKernel::W4_BF16:
+      return bore_with_flavour(WideFlavours{}, p.flavour, [&](auto S) { return launch(lbfgsb_kernel<S(), true>); });
+    case RestartKernel::OCC2:
+      return bore_with_flavour(NarrowWavesFlavours{}, p.flavour, [&](auto S) { return launch(lbfgsb_kernel_occ2<S()>); });
+    case RestartKernel::W4_F32: break;
+  }
+  return bore_with_flavour(AcqFlavours{}, p.flavour, [&](auto S) { return launch(lbfgsb_kernel<S()>); });
 }
 
 // ---------------------------------------------------------------------------

@@ -487,9 +487,9 @@ struct IterPlan {
 static int iteration_plan(const IterEngine &E, const Worker &w, int n_slots, IterArgs *h, IterPlan *plan) {
   if (!g_batch) return fail(BORE_E_INVALID, "iteration_launch: no batch set");
   const int64_t cap = g_batch->cap;
-  size_t ls = 0, lb = 0;
-  int ss = 0, sb = 0, blocks = 0;
   FitPlan fit;
+  ScreenPlan screen;
+  LbfgsbPlan restarts;
   int rc = fit_build(FitRequest{E.desc, n_slots, E.theta, E.adam_m, E.adam_v, E.adam_t, E.X32, E.z, cap, E.epochs,
                                 E.batch_size, nullptr, E.seed, E.loop_id0, 0, E.adam, nullptr},
                      fit);
@@ -498,14 +498,16 @@ static int iteration_plan(const IterEngine &E, const Worker &w, int n_slots, Ite
   const size_t lf = fit.lds_floats;
   const int sf = fit.flavour;
   const SampleSpec spec{E.seed, E.loop_id0, 0, E.low, E.high};
-  if ((rc = screen_build(E.desc, n_slots, E.theta, nullptr, &spec, E.num_samples, 0, E.num_starts, w.x0, w.idx,
-                         nullptr, h->s, ls, ss)))
+  // (batch mode: none of the forced choices applies, and the restarts run as a phase of the fused kernel -- four waves)
+  if ((rc = screen_build(ScreenRequest{E.desc, n_slots, E.theta, nullptr, &spec, E.num_samples, 0, E.num_starts, w.x0,
+                                       w.idx, nullptr}, AcqKnobs{}, screen)) ||
+      (rc = lbfgsb_build(LbfgsbRequest{E.desc, n_slots, E.theta, E.transform, 1, w.x0, E.num_starts, E.low, E.high,
+                                       E.opts, w.x, w.fun, w.jac, w.info}, AcqKnobs{}, false, restarts)))
     return rc;
-  if ((rc = lbfgsb_build(E.desc, n_slots, E.theta, E.transform, 1, w.x0, E.num_starts, E.low, E.high, E.opts, w.x,
-                         w.fun, w.jac, w.info, h->b, lb, sb, blocks)))
-    return rc;
+  h->s = screen.a; h->b = restarts.a;
+  const size_t ls = screen.lds_floats, lb = restarts.lds_floats;
   const int shape = iteration_shape(E.desc);
-  if (!shape || sf != shape || ss != shape || sb != shape || blocks != 1)
+  if (!shape || sf != shape || screen.flavour != shape || restarts.flavour != shape || restarts.blocks != 1)
     return fail(BORE_E_UNSUPPORTED, "iteration_launch: static shape 1, or 5 at 16 inputs, one workgroup per loop");
   h->X_seen = E.X_seen; h->y_seen = E.y_seen; h->X32 = E.X32; h->z = E.z;
   h->x_new = w.d_dbl; h->y_new = w.d_dbl + (size_t)E.n_loops * E.desc->input_dim;

@@ -936,8 +936,8 @@ extern "C" int bore_lstm_stream_lbfgsb_minimize(const bore_lstm_desc *desc, int 
   const long long groups = ((long long)num_starts + waves - 1) / waves;
   const long long gy = stream_walkers(n_models, groups, A.ws_stride, false);  // (the restarts take no CU cap)
   // every round serves one request of every live problem: a wave's problems, one after another, each within the
-  // optimiser's own limit
-  A.max_rounds = ((groups + gy - 1) / gy) * ((long long)opts->maxfun + opts->maxls + 64);
+  // optimiser's own limit (lbfgsb_round_cap)
+  A.max_rounds = ((groups + gy - 1) / gy) * lbfgsb_round_cap(opts);
   hipStream_t st = (hipStream_t)stream;
   if (const int rc = allow_lds(bls::lstm_stream_lbfgsb_kernel, lds_bytes)) return rc;
   HIP_TRY(hipMallocAsync((void **)&A.ws, (size_t)n_models * gy * A.ws_stride * sizeof(float), st));

@@ -1014,8 +1014,8 @@ extern "C" int bore_stream_lbfgsb_minimize(const bore_mlp_desc *desc, int n_mode
   const int D = a.L.w[0];
   if (D > BORE_DIM_MAX)
     return fail(BORE_E_UNSUPPORTED, "%s: the restarts take D <= BORE_DIM_MAX = %d (got %d)", who, BORE_DIM_MAX, D);
-  if (const int rc = lbfgsb_check_args(desc, n_models, theta, transform, x0, num_starts, lb, ub, opts, x, fun, jac, info,
-                                       a.box, a.nbd, a.opt))
+  if (const int rc = lbfgsb_check_args(LbfgsbRequest{desc, n_models, theta, transform, negate, x0, num_starts, lb, ub, opts,
+                                                     x, fun, jac, info}, a.box, a.nbd, a.opt))
     return rc;
   // dynamic LDS beside the static StreamLds: the box, the votes, then per wave the parked State and the optimiser's
   // fp64 and int workspaces -- every region a multiple of 16 bytes
@@ -1048,8 +1048,8 @@ extern "C" int bore_stream_lbfgsb_minimize(const bore_mlp_desc *desc, int n_mode
   const long long groups = ((long long)num_starts + waves - 1) / waves;
   const long long gy = stream_walkers(n_models, groups, a.ws_stride, false);  // (the restarts take no CU cap)
   // every round serves one request of every live problem: a wave's problems, one after another, each within the
-  // optimiser's own limit (lbfgsb_build's cap)
-  a.max_rounds = ((groups + gy - 1) / gy) * ((long long)opts->maxfun + opts->maxls + 64);
+  // optimiser's own limit (lbfgsb_round_cap)
+  a.max_rounds = ((groups + gy - 1) / gy) * lbfgsb_round_cap(opts);
   hipStream_t st = (hipStream_t)stream;
   if (const int rc = allow_lds(stream_lbfgsb_kernel, lds_bytes)) return rc;
   HIP_TRY(hipMallocAsync((void **)&a.ws, (size_t)n_models * gy * a.ws_stride * sizeof(float), st));
