@@ -1298,7 +1298,10 @@ static int lbfgsb_plan(const bore_mlp_desc *desc, int n_models, int num_starts, 
     const size_t fixed = off - (size_t)a.prob_floats * PB;   // everything but the problems (floats)
     int PB2 = (int)((BORE_LDS_BYTES / 4 - fixed) / small_f);
     if (PB2 > 8) PB2 = 8;
-    if (PB2 >= 1 && (knobs.big < 0 ? PB2 > PB : knobs.big != 0)) {
+    // (more than four slots, forced or not: with four or fewer the launch below goes to the four-wave kernel, whose
+    // body has no pool -- BIG_OK -- and would lay the matrices inside blocks carved without them: at maxcor 32 one or
+    // two problems fit even pooled.  tests/test_acq_plan_host.py)
+    if (PB2 > 4 && (knobs.big < 0 ? PB2 > PB : knobs.big != 0)) {
       p.pool_doubles = 8 * (size_t)lbfgsb::big_size(m);
       off = carve(PB = PB2, true);
       if (off * 4 > BORE_LDS_BYTES) return fail(BORE_E_UNSUPPORTED, "lbfgsb_minimize: LDS carve with the pooled matrices");
@@ -1321,6 +1324,10 @@ static int lbfgsb_plan(const bore_mlp_desc *desc, int n_models, int num_starts, 
     if (per_model > most) per_model = most;
     if (per_model < 1) per_model = 1;
     PB = (int)((num_starts + per_model - 1) / per_model);
+    // (fewer than four workspaces -- a large maxcor, or weights that leave room for one to three problems: no queue.
+    // lbfgsb_body starts wave wv < min(waves, problems) on problem wv in slot wv, and these launches have four waves:
+    // waves slots..3 would run in blocks that were never carved.  One workgroup per `slots` restarts instead.)
+    if (PB > slots && slots < 4) PB = slots;
     a.queue = PB > slots;
   }
   a.PB = PB;
@@ -1402,6 +1409,37 @@ extern "C" int bore_lbfgsb_minimize(const bore_mlp_desc *desc, int n_models, con
     case RestartKernel::W4_F32: break;
   }
   return bore_with_flavour(AcqFlavours{}, p.flavour, [&](auto S) { return launch(lbfgsb_kernel<S()>); });
+}
+
+// What bore_lbfgsb_minimize (many_waves != 0) or the fused iteration kernel (0) would launch for these sizes: lbfgsb_plan
+// asked with the knobs read as the entry point reads them, the CU count given, and -- batch_mode != 0 -- a complete
+// bore_batch of pointers that are never looked at.  Host only: no HIP call, no allocation.
+extern "C" int bore_lbfgsb_plan_query(const bore_mlp_desc *desc, int n_models, int num_starts, int maxcor, int cus,
+                                      int batch_mode, int many_waves, int32_t *out, int n_out) {
+  if (!desc || !out) return fail(BORE_E_INVALID, "lbfgsb_plan_query: null pointer");
+  if (n_out < BORE_LBFGSB_PLAN_FIELDS)
+    return fail(BORE_E_INVALID, "lbfgsb_plan_query: out holds fewer than %d fields", BORE_LBFGSB_PLAN_FIELDS);
+  if (n_models < 1) return fail(BORE_E_INVALID, "n_models must be >= 1 (got %d)", n_models);
+  if (cus < 1) return fail(BORE_E_INVALID, "lbfgsb_plan_query: cus < 1");
+  if (desc->input_dim < 1 || desc->input_dim > BORE_DIM_MAX)
+    return fail(BORE_E_UNSUPPORTED, "lbfgsb_minimize: input_dim must be 1..%d", BORE_DIM_MAX);
+  if (num_starts < 1) return fail(BORE_E_INVALID, "lbfgsb_minimize: num_starts < 1");
+  if (maxcor < 1 || maxcor > 32) return fail(BORE_E_UNSUPPORTED, "lbfgsb_minimize: maxcor must be 1..32");
+  static int32_t dummy_i[1];
+  static double dummy_d[1];
+  bore_batch bb{};
+  bb.ids = bb.its = dummy_i; bb.result = dummy_d; bb.flag = dummy_i; bb.cap = 64;
+  LbfgsbPlan p;
+  if (const int rc = lbfgsb_plan(desc, n_models, num_starts, maxcor, acq_knobs(), cus, batch_mode ? &bb : nullptr,
+                                 many_waves != 0, p))
+    return rc;
+  const LbfgsbArgs &a = p.a;
+  const long long fields[BORE_LBFGSB_PLAN_FIELDS] = {
+      (long long)p.kernel, p.flavour, p.slots, p.waves, p.blocks, (long long)p.lds_floats, (long long)p.pool_doubles, a.PB,
+      a.queue, a.o_tile, a.o_vals, a.o_box, a.o_prob, a.o_state, a.o_dw, a.o_iw, a.o_res, a.o_queue, a.o_layout,
+      a.prob_floats, a.total};
+  for (int i = 0; i < BORE_LBFGSB_PLAN_FIELDS; ++i) out[i] = (int32_t)fields[i];
+  return 0;
 }
 
 // ---------------------------------------------------------------------------

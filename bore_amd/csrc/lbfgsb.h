@@ -84,7 +84,8 @@ struct State {
 #endif
 };
 
-// Every sub-array starts on a 16-byte boundary (vectors are padded to an even length) and the
+// Every sub-array starts on a 16-byte boundary (vectors are padded to an even length -- the m-long reciprocals of an
+// odd maxcor as well: tests/test_lbfgsb_host.py holds the layout to that) and the
 // caller must hand in a 16-byte aligned base: the device compiler merges adjacent fp64 LDS
 // loads into ds_read_b128, which returns WRONG data at 8-byte alignment on gfx950 (found as a
 // host/device mismatch for odd n; see tests/test_gpu_argmax.py).
@@ -101,8 +102,10 @@ struct State {
 // the LDS) instead of inside dw.
 LB_HD int big_size(int m) { return 2 * m * (2 * m + 1); }
 LB_HD int dwork_size(int n, int m, bool big_outside = false) {
-  const int ne = (n + 1) & ~1, mne = (m * n + 1) & ~1, mm = (m * m + 1) & ~1;
-  return 2 * mne + 3 * mm + (big_outside ? 0 : big_size(m)) + 8 * m + 9 * ne + 6 * m;
+  const int ne = (n + 1) & ~1, mne = (m * n + 1) & ~1, mm = (m * m + 1) & ~1, me = (m + 1) & ~1;
+  // (the reciprocals: rwt | rwn | rsy | rsq = 2 m + 3 me doubles, in the 6 m an even m has always had; m = 1 needs 8)
+  const int recip = 2 * m + 3 * me > 6 * m ? 2 * m + 3 * me : 6 * m;
+  return 2 * mne + 3 * mm + (big_outside ? 0 : big_size(m)) + 8 * m + 9 * ne + recip;
 }
 LB_HD int iwork_size(int n) { return 3 * n; }
 
@@ -128,7 +131,7 @@ struct Work {
 
 LB_HD Work make_work(double *dw, int *iw, int n, int m, double *big = nullptr) {
   Work w;
-  const int ne = (n + 1) & ~1, mne = (m * n + 1) & ~1, mm = (m * m + 1) & ~1;
+  const int ne = (n + 1) & ~1, mne = (m * n + 1) & ~1, mm = (m * m + 1) & ~1, me = (m + 1) & ~1;
   w.ws = dw; dw += mne;
   w.wy = dw; dw += mne;
   w.sy = dw; dw += mm;
@@ -151,9 +154,9 @@ LB_HD Work make_work(double *dw, int *iw, int n, int m, double *big = nullptr) {
   w.xlast = dw; dw += ne;
   w.glast = dw; dw += ne;
   w.wa = dw; dw += 8 * m;
-  w.rwt = dw; dw += m;
+  w.rwt = dw; dw += me;
   w.rwn = dw; dw += 2 * m;
-  w.rsy = dw; dw += m;
+  w.rsy = dw; dw += me;
   w.rsq = dw;
   w.index = iw;
   w.iwhere = iw + n;

@@ -256,6 +256,25 @@ int bore_lbfgsb_minimize(const bore_mlp_desc *desc, int n_models, const float *t
                          double *x, double *fun, double *jac, int32_t *info, void *stream);
 
 /*
+ * What bore_lbfgsb_minimize would launch for a request of these sizes, as integers (tests: the carve against what the
+ * kernels index).  Host only: no HIP call, no allocation, no pointer of a request; the BORE_LBFGSB_* knobs are read as
+ * the entry point reads them.
+ *   cus         compute units to plan for (the entry point asks the device)
+ *   batch_mode  != 0: as under bore_set_batch with a complete bore_batch
+ *   many_waves  != 0: bore_lbfgsb_minimize's launch (eight- and twelve-wave kernels allowed); 0: the fused
+ *               iteration kernel's restart phase
+ *   out         int32 [n_out >= BORE_LBFGSB_PLAN_FIELDS]: kernel (0 four-wave float32, 1 four-wave bfloat16,
+ *               2 two workgroups per CU, 3 eight-wave float32, 4 eight-wave bfloat16, 5 twelve-wave), flavour, slots
+ *               (workspaces carved), waves, blocks (grid.y), lds_floats, pool_doubles (per pool slot; 0: no pool), PB
+ *               (problems per workgroup), queue, then the carve in floats: o_tile, o_vals, o_box, o_prob, o_state, o_dw,
+ *               o_iw, o_res, o_queue, o_layout, prob_floats, total
+ * Returns what the entry point's planning returns (0, or its refusal with its message).
+ */
+#define BORE_LBFGSB_PLAN_FIELDS 21
+int bore_lbfgsb_plan_query(const bore_mlp_desc *desc, int n_models, int num_starts, int maxcor, int cus,
+                           int batch_mode, int many_waves, int32_t *out, int n_out);
+
+/*
  * Record.append + Record.load_regression_data for replica runs (bore/data.py:14-29): the
  * device keeps every loop's observations in fp64, X_seen [n_models][cap][D] and y_seen
  * [n_models][cap] (the first n_seen rows valid).  This call appends row n_seen = (x_new, y_new)

@@ -27,6 +27,17 @@ def lib():
     return _lib
 
 
+LAYOUT_NAMES = ("ws wy sy ss wt snd wn z r d t xp x g xlast glast wa rwt rwn rsy rsq").split()
+
+
+def layout(n, m, big_outside=False):
+    """make_work's layout for (n, m): ({pointer name: offset in doubles from dw -- snd / wn from `big` when big_outside},
+    {int array: offset from iw}, dwork_size, big_size, iwork_size)."""
+    off, ioff, sizes = (C.c_int * 21)(), (C.c_int * 3)(), (C.c_int * 3)()
+    lib().lbfgsb_host_layout(int(n), int(m), int(bool(big_outside)), off, ioff, sizes)
+    return (dict(zip(LAYOUT_NAMES, off)), dict(zip(("index", "iwhere", "indx2"), ioff)), sizes[0], sizes[1], sizes[2])
+
+
 def minimize(fun, x0, bounds, maxcor=10, ftol=2.2204460492503131e-09, gtol=1e-5, maxfun=15000,
              maxiter=15000, maxls=20, form=0):
     """fun(x) -> (f, g).  bounds: (lb, ub) arrays with +-inf for open sides.

@@ -63,6 +63,28 @@ int lbfgsb_host_minimize_form(int form, int n, int m, const double *x0, const do
   return rounds;
 }
 
+// The workspace layout of make_work for (n, m): the offset in doubles of every pointer it sets, relative to dw -- snd
+// and wn relative to `big` when big_outside -- in the order ws wy sy ss wt snd wn z r d t xp x g xlast glast wa rwt rwn
+// rsy rsq (21), the three int arrays' offsets relative to iw (3), and sizes = {dwork_size, big_size, iwork_size}.
+void lbfgsb_host_layout(int n, int m, int big_outside, int *offsets, int *int_offsets, int *sizes) {
+  using namespace lbfgsb;
+  std::vector<double> dw(dwork_size(n, m, big_outside != 0)), big(big_size(m));
+  std::vector<int> iw(iwork_size(n));
+  const Work w = make_work(dw.data(), iw.data(), n, m, big_outside ? big.data() : nullptr);
+  const double *mat = big_outside ? big.data() : dw.data();
+  const double *const ptrs[21] = {w.ws, w.wy, w.sy, w.ss, w.wt, nullptr, nullptr, w.z, w.r, w.d, w.t, w.xp, w.x, w.g,
+                                  w.xlast, w.glast, w.wa, w.rwt, w.rwn, w.rsy, w.rsq};
+  for (int i = 0; i < 21; ++i) offsets[i] = ptrs[i] ? (int)(ptrs[i] - dw.data()) : 0;
+  offsets[5] = (int)(w.snd - mat);
+  offsets[6] = (int)(w.wn - mat);
+  int_offsets[0] = (int)(w.index - iw.data());
+  int_offsets[1] = (int)(w.iwhere - iw.data());
+  int_offsets[2] = (int)(w.indx2 - iw.data());
+  sizes[0] = dwork_size(n, m, big_outside != 0);
+  sizes[1] = big_size(m);
+  sizes[2] = iwork_size(n);
+}
+
 // Returns the number of state-machine round trips.  out_i = {nit, nfev, status, task, msg}.
 int lbfgsb_host_minimize(int n, int m, const double *x0, const double *l, const double *u,
                          const int *nbd, double factr, double pgtol, int maxiter, int maxfun,

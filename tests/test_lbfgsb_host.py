@@ -229,3 +229,111 @@ def test_counting_build_runs_the_same_optimisation(tmp_path):
         assert (int(oi[0]), int(oi[1]), int(oi[2])) == (ref.nit, ref.nfev, ref.status)
         assert np.array_equal(xo, ref.x) and fo.value == ref.fun
         assert oc[0] > 100 * ref.nit and 0 < oc[1] < oc[0]
+
+
+# ---- the workspace layout (make_work / dwork_size) and every maxcor ------------------------------------------------
+def _documented_lengths(n, m):
+    """Lengths in doubles of make_work's sub-arrays, in the order it lays them out, as lbfgsb.h documents them."""
+    vectors = [(v, n) for v in "z r d t xp x g xlast glast".split()]
+    return ([("ws", m * n), ("wy", m * n), ("sy", m * m), ("ss", m * m), ("wt", m * m),
+             ("snd", 2 * m * (2 * m + 1))] + vectors + [("wa", 8 * m), ("rwt", m), ("rwn", 2 * m), ("rsy", m), ("rsq", m)])
+
+
+def _layout_before_padding(n, m, big_outside):
+    """The offsets and dwork_size as they stood before odd maxcor was padded: what every even maxcor keeps exactly."""
+    ne, mne, mm = (n + 1) & ~1, (m * n + 1) & ~1, (m * m + 1) & ~1
+    big = 2 * m * (2 * m + 1)
+    off, at = {}, 0
+    for name, step in ([("ws", mne), ("wy", mne), ("sy", mm), ("ss", mm), ("wt", mm)]
+                       + ([] if big_outside else [("snd", big)])
+                       + [(v, ne) for v in "z r d t xp x g xlast glast".split()]
+                       + [("wa", 8 * m), ("rwt", m), ("rwn", 2 * m), ("rsy", m), ("rsq", m)]):
+        off[name] = at
+        at += step
+    if big_outside:
+        off["snd"] = 0
+    off["wn"] = off["snd"] + 2 * m
+    return off, 2 * mne + 3 * mm + (0 if big_outside else big) + 8 * m + 9 * ne + 6 * m
+
+
+@pytest.mark.parametrize("big_outside", [False, True])
+def test_workspace_layout_is_ordered_disjoint_and_16_byte_aligned(big_outside):
+    """lbfgsb.h promises every sub-array a 16-byte boundary (merged fp64 LDS loads return wrong data at 8 mod 16 on
+    gfx950): for every n in 1..64 and maxcor in 1..32 the pointers make_work sets come in order, do not overlap at
+    their documented lengths, end inside dwork_size, and start at even offsets; the sizes are even; an even maxcor
+    has the offsets and the size it has always had."""
+    bad = []
+    for n in range(1, 65):
+        for m in range(1, 33):
+            off, ioff, dsize, bsize, isize = H.layout(n, m, big_outside)
+            assert bsize == 2 * m * (2 * m + 1) and isize == 3 * n
+            assert ioff == dict(index=0, iwhere=n, indx2=2 * n)
+            assert off["wn"] == off["snd"] + 2 * m          # two triangles of ONE (2m) x (2m + 1) block
+            order = _documented_lengths(n, m)
+            if big_outside:
+                assert off["snd"] == 0                          # (relative to `big`, whose big_size doubles hold it)
+                order = [(k, l) for k, l in order if k != "snd"]
+            at = 0
+            for name, length in order:
+                if off[name] < at:
+                    bad.append((n, m, name, "overlaps its predecessor", off[name], at))
+                if off[name] % 2:
+                    bad.append((n, m, name, "starts at an odd offset", off[name]))
+                at = off[name] + length
+            if order[0][0] != "ws" or off["ws"] != 0:
+                bad.append((n, m, "ws", "is not the first"))
+            if at > dsize:
+                bad.append((n, m, "rsq", "ends past dwork_size", at, dsize))
+            if dsize % 2 or bsize % 2:
+                bad.append((n, m, "sizes", "odd", dsize, bsize))
+            if m % 2 == 0:
+                want_off, want_size = _layout_before_padding(n, m, big_outside)
+                if off != want_off or dsize != want_size:
+                    bad.append((n, m, "even maxcor", "moved", dsize, want_size))
+    assert not bad, (len(bad), sorted({(m, name) for _, m, name, *_ in bad})[:12], bad[:4])
+
+
+_ROSEN_RUNS = {}
+
+
+def _rosenbrock_runs(maxcor):
+    """SciPy and the host build on Rosenbrock: n in {5, 10, 20} x the five boxes x four starts from RandomState(n),
+    45 iterations at the most, so that the history wraps for every maxcor below 45."""
+    if maxcor not in _ROSEN_RUNS:
+        runs = []
+        for n in (5, 10, 20):
+            for box in ("wide", "active", "free", "lower", "upper"):
+                rs = np.random.RandomState(n)
+                for _ in range(4):
+                    x0 = rs.uniform(-2, 2, size=n)
+                    lb, ub = np.full(n, -1.5), np.full(n, 2.0)
+                    if box == "active":
+                        ub[:] = 0.8
+                    elif box == "free":
+                        lb[:], ub[:] = -np.inf, np.inf
+                    elif box == "lower":
+                        ub[:] = np.inf
+                    elif box == "upper":
+                        lb[:] = -np.inf
+                    runs.append(both(lambda x: (rosen(x), rosen_der(x)), x0, lb, ub, maxiter=45, ftol=1e-9,
+                                     maxcor=maxcor))
+        _ROSEN_RUNS[maxcor] = runs
+    return _ROSEN_RUNS[maxcor]
+
+
+@pytest.mark.parametrize("maxcor", [1, 2, 3, 5, 7, 9, 11, 13, 17, 23, 31, 32])
+def test_same_trajectory_as_scipy_for_every_maxcor(maxcor):
+    """The history length is the workspace layout, the loop bounds of the compact representation and the wrap-around of
+    the circular history: SciPy's (nit, nfev, status) on all 60 runs, its x to 1e-4 (measured worst case 1.8e-5 with
+    SciPy 1.15.3: rounding over 45 iterations; the bound test_limits_and_status_codes_match_scipy has for maxcor 1), and
+    the premise -- at least half the runs outlast the history, so that it wraps."""
+    runs = _rosenbrock_runs(maxcor)
+    assert len(runs) == 60
+    worst = 0.0
+    for a, b in runs:
+        assert (a.nit, a.nfev, a.status) == (b.nit, b.nfev, b.status), (maxcor, a.x.size)
+        worst = max(worst, float(np.max(np.abs(a.x - b.x))))
+    print("maxcor %d: max |dx| %.3g, %d of 60 runs with nit > maxcor"
+          % (maxcor, worst, sum(b.nit > maxcor for _, b in runs)))
+    assert worst <= 1e-4
+    assert sum(b.nit > maxcor for _, b in runs) >= 30
