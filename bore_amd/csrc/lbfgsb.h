@@ -280,6 +280,19 @@ struct LbLocalClock { long long lb_last; };
 #define CK_MARK(i) ((void)0)
 #endif
 
+// Which bound kinds and recovery branches a run took: LB_EVENT(s, id) stands where both the sequential and the
+// cooperating-wave form pass.  Nothing unless the including file defines LBFGSB_HOST_EVENTS -- and then LB_EVENT
+// itself: the host build of tests/native/lbfgsb_host.cpp counts them; no device build does.
+enum {
+  EV_PROJECTED_START = 0, EV_FIXED_VARIABLE, EV_FREE_VARIABLE, EV_UNCONSTRAINED_ITERATION, EV_FIRST_STEP_NOT_BOXED,
+  EV_CAUCHY_SINGULAR_REFRESH, EV_FORMK_REFRESH, EV_CMPRLB_REFRESH, EV_SUBSM_REFRESH, EV_FORMT_REFRESH,
+  EV_SUBSM_HIT_BOUND, EV_SUBSM_BACKTRACK, EV_NFREE_ZERO, EV_ENTER, EV_LEAVE, EV_LS_CACHE_HIT, EV_LS_NOT_DESCENT,
+  EV_LS_MAXLS, EV_LS_FAIL_REFRESH, EV_ABNORMAL, EV_UPDATE_SKIPPED, EV_INFO_MINUS5, EV_HISTORY_WRAPPED, EV_COUNT
+};
+#if !defined(LBFGSB_HOST_EVENTS)
+#define LB_EVENT(s_, id) ((void)0)
+#endif
+
 // The value `v` holds in lane `src` (wave-uniform), in every lane of the wave.
 #if defined(__HIP_DEVICE_COMPILE__)
 LB_HD double lane_bcast(double v, int src) {
@@ -1394,6 +1407,7 @@ LB_HDN int subsm(const IterArgs s, const Work w, const double *l, const double *
     for (int i = 0; i < n; ++i) dd_p += (x[i] - xx[i]) * gg[i];
   }
   if (dd_p > 0.0) {  // not a descent direction: fall back to the backtracking step
+    LB_EVENT(s, EV_SUBSM_BACKTRACK);
     for (int i = 0; i < n; ++i) x[i] = xp[i];
     double alpha = 1.0, temp1 = alpha;
     int ibd = 0;
@@ -1952,6 +1966,13 @@ LB_HD int lbfgsb_advance(State &s, const Work &w, const double *l, const double 
       }
     }
     }
+    if (s.prjctd) LB_EVENT(s, EV_PROJECTED_START);
+#if defined(LBFGSB_HOST_EVENTS)
+    for (int i = 0, fixed = 0, open = 0; i < n; ++i) {  // (once per problem each)
+      if (w.iwhere[i] == 3 && !fixed++) LB_EVENT(s, EV_FIXED_VARIABLE);
+      if (w.iwhere[i] == -1 && !open++) LB_EVENT(s, EV_FREE_VARIABLE);
+    }
+#endif
     s.stage = S_FG_START;
     s.task = T_FG;
     ++s.nfev;
@@ -1994,6 +2015,7 @@ LB_HD int lbfgsb_advance(State &s, const Work &w, const double *l, const double 
       s.ifun = s.iback = 0;
       s.iword = -1;
       if (!s.cnstnd && s.col > 0) {
+        LB_EVENT(s, EV_UNCONSTRAINED_ITERATION);
         for (int i = coop.lane; i < n; i += coop.nl) w.z[i] = w.x[i];
         LB_LANES_SYNC();
         s.wrk = s.updatd;
@@ -2007,6 +2029,7 @@ LB_HD int lbfgsb_advance(State &s, const Work &w, const double *l, const double 
         LB_PHASE_END(0);
         s.nseg = rc >> 8;
         if (rc & 0xff) {  // singular triangular system: refresh the memory
+          LB_EVENT(s, EV_CAUCHY_SINGULAR_REFRESH);
           refresh_memory(s);
           continue;
         }
@@ -2015,8 +2038,11 @@ LB_HD int lbfgsb_advance(State &s, const Work &w, const double *l, const double 
           freev<VL>(s, w, coop);
           LB_PHASE_END(8);
         }
+        if (s.nenter > 0) LB_EVENT(s, EV_ENTER);
+        if (s.ileave < n + 1) LB_EVENT(s, EV_LEAVE);
         s.nact = n - s.nfree;
       }
+      if (s.nfree == 0) LB_EVENT(s, EV_NFREE_ZERO);
       if (s.nfree != 0 && s.col != 0) {
         const IterArgs ia{n, m, LB_UNI(s.col, coop), LB_UNI(s.head, coop), LB_UNI(s.nfree, coop),
                           LB_UNI(s.nenter, coop), LB_UNI(s.ileave, coop), LB_UNI(s.updatd, coop),
@@ -2029,14 +2055,14 @@ LB_HD int lbfgsb_advance(State &s, const Work &w, const double *l, const double 
           }
           const int fk = formk(ia, w);
           LB_PHASE_END(1);
-          if (fk) { refresh_memory(s); continue; }
+          if (fk) { LB_EVENT(s, EV_FORMK_REFRESH); refresh_memory(s); continue; }
         }
         int rc;
         {
           LB_PHASE_BEGIN(24);
           const int cm = cmprlb(s, w, coop);
           LB_PHASE_END(2);
-          if (cm) { refresh_memory(s); continue; }
+          if (cm) { LB_EVENT(s, EV_CMPRLB_REFRESH); refresh_memory(s); continue; }
         }
         {
           LB_PHASE_BEGIN(25);
@@ -2044,7 +2070,8 @@ LB_HD int lbfgsb_advance(State &s, const Work &w, const double *l, const double 
           LB_PHASE_END(3);
         }
         s.iword = rc >> 8;
-        if (rc & 0xff) { refresh_memory(s); continue; }
+        if (rc & 0xff) { LB_EVENT(s, EV_SUBSM_REFRESH); refresh_memory(s); continue; }
+        if (s.iword == 1) LB_EVENT(s, EV_SUBSM_HIT_BOUND);
       }
       {
         LB_PHASE_BEGIN(26);
@@ -2062,6 +2089,7 @@ LB_HD int lbfgsb_advance(State &s, const Work &w, const double *l, const double 
       ls_rc = lnsrlb<VL>(s, w, l, u, nbd, first_ls ? 1 : 0, coop);
       LB_PHASE_END(4);
     }
+    if (first_ls && s.iter == 0 && !s.boxed) LB_EVENT(s, EV_FIRST_STEP_NOT_BOXED);  // (stp = min(1 / dnorm, stpmx))
     if constexpr (TWO) {
       if (ls_rc && n == 2) {
         // ---- the rest of this search in registers (see the header of this function) ----
@@ -2074,6 +2102,7 @@ LB_HD int lbfgsb_advance(State &s, const Work &w, const double *l, const double 
           // SciPy's ScalarFunction cache: a request at the point evaluated last is served from it
           const bool differs = (x0 != xl0) || (x1 != xl1);
           if (!differs) {
+            LB_EVENT(s, EV_LS_CACHE_HIT);
             s.f = s.flast;
             g0 = gl0;
             g1 = gl1;
@@ -2147,6 +2176,7 @@ LB_HD int lbfgsb_advance(State &s, const Work &w, const double *l, const double 
         const bool cached = coop.nl > 1 ? !lanes_any(differs) : !differs;
         LB_PHASE_END(10);
         if (cached) {
+          LB_EVENT(s, EV_LS_CACHE_HIT);
           s.f = s.flast;
           for (int i = coop.lane; i < n; i += coop.nl) w.g[i] = w.glast[i];
           LB_LANES_SYNC();
@@ -2171,6 +2201,8 @@ LB_HD int lbfgsb_advance(State &s, const Work &w, const double *l, const double 
     }
     if (s.info != 0 || s.iback >= opt.maxls) {
       // restore the previous iterate
+      if (s.info == -4) LB_EVENT(s, EV_LS_NOT_DESCENT);
+      if (s.info == 0) LB_EVENT(s, EV_LS_MAXLS);
       for (int i = coop.lane; i < n; i += coop.nl) { w.x[i] = w.t[i]; w.g[i] = w.r[i]; }
       LB_LANES_SYNC();
       s.f = s.fold;
@@ -2178,9 +2210,11 @@ LB_HD int lbfgsb_advance(State &s, const Work &w, const double *l, const double 
         // abnormal termination
         if (s.info == 0) { s.info = -9; --s.nfgv; --s.ifun; --s.iback; }
         ++s.iter;
+        LB_EVENT(s, EV_ABNORMAL);
         finish(s, T_ABNORMAL, M_NONE);
         return LB_DONE;
       }
+      LB_EVENT(s, EV_LS_FAIL_REFRESH);
       refresh_memory(s);  // restart from the steepest-descent-like state
       continue;
     }
@@ -2200,7 +2234,7 @@ LB_HD int lbfgsb_advance(State &s, const Work &w, const double *l, const double 
     {
       const double ddum = fmax(fmax(fabs(s.fold), fabs(s.f)), 1.0);
       if ((s.fold - s.f) <= LB_EPSMCH * opt.factr * ddum) {
-        if (s.iback >= 10) s.info = -5;
+        if (s.iback >= 10) { s.info = -5; LB_EVENT(s, EV_INFO_MINUS5); }
         finish(s, T_CONVERGENCE, M_FACTR);
         return LB_DONE;
       }
@@ -2223,11 +2257,13 @@ LB_HD int lbfgsb_advance(State &s, const Work &w, const double *l, const double 
       }
       if (dr <= LB_EPSMCH * ddum) {  // curvature too small: skip the update
         s.updatd = 0;
+        LB_EVENT(s, EV_UPDATE_SKIPPED);
         continue;
       }
       s.updatd = 1;
       ++s.iupdat;
       LB_PHASE_END(11);
+      if (s.col == m) LB_EVENT(s, EV_HISTORY_WRAPPED);  // (matupd drops the oldest pair)
       {
         LB_PHASE_BEGIN(31);
         matupd<VL>(s, w, rr, dr, coop);
@@ -2240,6 +2276,7 @@ LB_HD int lbfgsb_advance(State &s, const Work &w, const double *l, const double 
         LB_PHASE_END(6);
       }
       if (ft) {
+        LB_EVENT(s, EV_FORMT_REFRESH);
         refresh_memory(s);
         continue;
       }

@@ -24,9 +24,16 @@ def lib():
         _lib = C.CDLL(SO)
         _lib.lbfgsb_host_minimize.restype = C.c_int
         _lib.lbfgsb_host_minimize_form.restype = C.c_int
+        _lib.lbfgsb_host_minimize_events.restype = C.c_int
+        assert _lib.lbfgsb_host_event_count() == len(EVENT_NAMES)
     return _lib
 
 
+# the events lbfgsb.h reports to the host build, in the order of its EV_* enum
+EVENT_NAMES = ("projected_start fixed_variable free_variable unconstrained_iteration first_step_not_boxed "
+               "cauchy_singular_refresh formk_refresh cmprlb_refresh subsm_refresh formt_refresh subsm_hit_bound "
+               "subsm_backtrack nfree_zero enter leave ls_cache_hit ls_not_descent ls_maxls ls_fail_refresh abnormal "
+               "update_skipped info_minus5 history_wrapped").split()
 LAYOUT_NAMES = ("ws wy sy ss wt snd wn z r d t xp x g xlast glast wa rwt rwn rsy rsq").split()
 
 
@@ -39,10 +46,11 @@ def layout(n, m, big_outside=False):
 
 
 def minimize(fun, x0, bounds, maxcor=10, ftol=2.2204460492503131e-09, gtol=1e-5, maxfun=15000,
-             maxiter=15000, maxls=20, form=0):
+             maxiter=15000, maxls=20, form=0, events=False):
     """fun(x) -> (f, g).  bounds: (lb, ub) arrays with +-inf for open sides.
     form: 0 reverse communication, 1 the routine calls the evaluation (DIRECT), 2 DIRECT with the
-    two-variable line search in registers (lbfgsb.h)."""
+    two-variable line search in registers (lbfgsb.h).
+    events: also res.events, {name: how often the run passed that LB_EVENT of lbfgsb.h} for EVENT_NAMES."""
     x0 = np.ascontiguousarray(x0, dtype=np.float64)
     n = x0.size
     lb, ub = (np.broadcast_to(np.asarray(b, dtype=np.float64), n).copy() for b in bounds)
@@ -65,9 +73,16 @@ def minimize(fun, x0, bounds, maxcor=10, ftol=2.2204460492503131e-09, gtol=1e-5,
     fo = C.c_double()
     oi = np.zeros(5, dtype=np.int32)
     dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
-    lib().lbfgsb_host_minimize_form(int(form), n, maxcor, dp(x0), dp(l), dp(u), nbd.ctypes.data_as(C.POINTER(C.c_int)),
-                               C.c_double(ftol / np.finfo(float).eps), C.c_double(gtol), maxiter,
-                               maxfun, maxls, _CB(cb), dp(xo), C.byref(fo), dp(go),
-                               oi.ctypes.data_as(C.POINTER(C.c_int)))
-    return OptimizeResult(x=xo, fun=fo.value, jac=go, nit=int(oi[0]), nfev=int(oi[1]),
+    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+    args = (int(form), n, maxcor, dp(x0), dp(l), dp(u), ip(nbd), C.c_double(ftol / np.finfo(float).eps), C.c_double(gtol),
+            maxiter, maxfun, maxls, _CB(cb), dp(xo), C.byref(fo), dp(go), ip(oi))
+    if events:
+        ev = np.zeros(len(EVENT_NAMES), dtype=np.int32)
+        lib().lbfgsb_host_minimize_events(*args, ip(ev))
+    else:
+        lib().lbfgsb_host_minimize_form(*args)
+    res = OptimizeResult(x=xo, fun=fo.value, jac=go, nit=int(oi[0]), nfev=int(oi[1]),
                           status=int(oi[2]), success=oi[2] == 0, task=(int(oi[3]), int(oi[4])))
+    if events:
+        res.events = dict(zip(EVENT_NAMES, ev.tolist()))
+    return res

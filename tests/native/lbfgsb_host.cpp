@@ -4,7 +4,15 @@
 #include <cstdlib>
 #include <vector>
 
+// The events of lbfgsb.h (EV_*: bound kinds met, recovery branches taken) are counted here, per thread, and handed out
+// by lbfgsb_host_minimize_events; counting touches nothing the optimiser reads.
+#define LBFGSB_HOST_EVENTS
+static thread_local int lbfgsb_host_events[32];
+#define LB_EVENT(s_, id) ((void)++lbfgsb_host_events[id])
+
 #include "../../bore_amd/csrc/lbfgsb.h"
+
+static_assert(lbfgsb::EV_COUNT <= 32, "lbfgsb_host_events is too short");
 
 extern "C" {
 
@@ -115,6 +123,21 @@ int lbfgsb_host_minimize(int n, int m, const double *x0, const double *l, const 
   out_i[2] = s.status;
   out_i[3] = s.task;
   out_i[4] = s.msg;
+  return rounds;
+}
+
+// lbfgsb_host_minimize_form that also returns how often each event of lbfgsb.h occurred: out_events[EV_COUNT], in
+// the order of its enum (lbfgsb_host_event_count tells EV_COUNT).
+int lbfgsb_host_event_count() { return lbfgsb::EV_COUNT; }
+
+int lbfgsb_host_minimize_events(int form, int n, int m, const double *x0, const double *l, const double *u,
+                                const int *nbd, double factr, double pgtol, int maxiter, int maxfun,
+                                int maxls, fg_callback fg, double *x_out, double *f_out, double *g_out,
+                                int *out_i, int *out_events) {
+  for (int i = 0; i < lbfgsb::EV_COUNT; ++i) lbfgsb_host_events[i] = 0;
+  const int rounds = lbfgsb_host_minimize_form(form, n, m, x0, l, u, nbd, factr, pgtol, maxiter, maxfun, maxls, fg,
+                                               x_out, f_out, g_out, out_i);
+  for (int i = 0; i < lbfgsb::EV_COUNT; ++i) out_events[i] = lbfgsb_host_events[i];
   return rounds;
 }
 }

@@ -337,3 +337,100 @@ def test_same_trajectory_as_scipy_for_every_maxcor(maxcor):
           % (maxcor, worst, sum(b.nit > maxcor for _, b in runs)))
     assert worst <= 1e-4
     assert sum(b.nit > maxcor for _, b in runs) >= 30
+
+
+# ---- bound kinds and recovery paths: the event counters, and the premises of tests/test_gpu_lbfgsb_paths.py ---------
+import lbfgsb_paths as T  # noqa: E402
+
+_ORACLE_RUNS = {}
+
+
+def _oracle_runs(family):
+    """Every restart of every launch of `family` (tests/lbfgsb_paths.py) on the host build with the ORACLE's f and g:
+    [(net, pattern, tag, x0, lo, hi, options, record with events, every (x, f, g) evaluated)].  Computed once."""
+    if family not in _ORACLE_RUNS:
+        runs = []
+        for name in T.FAMILIES[family][0]:
+            for pattern, tag, lo, hi, X0, hard, maxcor in T.launches(family, name):
+                fg = T.oracle_fg(name, hard)
+                for x0 in X0:
+                    seen = []
+
+                    def traced(x, fg=fg, seen=seen):
+                        f, g = fg(x)
+                        seen.append((x.copy(), float(f), np.asarray(g, dtype=np.float64)))
+                        return f, g
+                    rec = H.minimize(traced, x0, (lo, hi), events=True, **T.opts_for(maxcor))
+                    runs.append((name, pattern, tag, x0, lo, hi, T.opts_for(maxcor), rec, seen))
+        _ORACLE_RUNS[family] = runs
+    return _ORACLE_RUNS[family]
+
+
+def test_event_counters_do_not_change_the_optimisation():
+    """events=True and events=False: the same record bit for bit in the three forms, on every bound kind, and the three
+    forms count the same events."""
+    def same(a, b):
+        return (np.array_equal(a.x, b.x) and a.fun == b.fun and np.array_equal(a.jac, b.jac)
+                and (a.nit, a.nfev, a.status, a.task) == (b.nit, b.nfev, b.status, b.task))
+    n_runs, seen = 0, {}
+    for name in ("2-16-16-1", "6-32-32-1"):
+        for pattern, tag, lo, hi, X0, hard, maxcor in T.launches("four_wave_static" if name[0] == "2" else "queue", name):
+            fg = T.oracle_fg(name, hard)
+            for x0 in X0[:3]:
+                counted = [H.minimize(fg, x0, (lo, hi), form=form, events=True, **T.opts_for(maxcor)) for form in range(3)]
+                for form in range(3):
+                    plain = H.minimize(fg, x0, (lo, hi), form=form, **T.opts_for(maxcor))
+                    assert not hasattr(plain, "events")
+                    assert same(plain, counted[form]), (name, pattern, tag, form)
+                    assert counted[form].events == counted[0].events, (name, pattern, tag, form)
+                T.add_events(seen, counted[0])
+                n_runs += 1
+    assert n_runs >= 50 and sum(v > 0 for v in seen.values()) >= 15, seen       # (the counters do count)
+    assert set(seen) == set(H.EVENT_NAMES)
+
+
+@pytest.mark.parametrize("family", list(T.FAMILIES))
+def test_premises_of_the_device_cases_are_met_three_times_with_the_oracle(family):
+    """With the oracle's f and g every per-family premise of tests/test_gpu_lbfgsb_paths.py is met at least THREE times
+    (the device's f and g differ from the oracle's in the last bits and move individual searches: the GPU file asks for
+    one), and every x, f and g of every run is finite with |x| <= 1e3: the open-sided problems do not run off."""
+    total = {}
+    for name, pattern, tag, x0, lo, hi, opts, rec, seen in _oracle_runs(family):
+        T.add_events(total, rec, x0, lo, hi)
+        for x, f, g in seen:
+            assert np.isfinite(x).all() and np.isfinite(f) and np.isfinite(g).all(), (name, pattern, tag)
+            assert np.abs(x).max() <= 1e3, (name, pattern, tag, x)
+        assert np.isfinite(rec.x).all() and np.isfinite(rec.fun) and np.isfinite(rec.jac).all()
+    print(family, {k: total.get(k, 0) for k in T.PER_FAMILY + T.WHOLE_FILE})
+    assert not [k for k in T.PER_FAMILY if total.get(k, 0) < 3], total
+    assert total["projected_start"] == 0      # (lbfgsb_init clips the start: the routine's own projection moves nothing)
+
+
+def test_whole_file_premises_are_met_three_times_with_the_oracle():
+    total = {}
+    for family in T.FAMILIES:
+        for run in _oracle_runs(family):
+            T.add_events(total, run[7])
+    assert not [k for k in T.WHOLE_FILE if total.get(k, 0) < 3], total
+    many = {f: sum(r[7].events["formk_refresh"] for r in _oracle_runs(f)) for f in ("twelve_waves", "eight_waves_float32")}
+    assert min(many.values()) >= 3, many
+
+
+def test_bound_patterns_match_scipy_statistics():
+    """SciPy parity on the bound kinds: the float32 nets of the table under patterns a-e (soft weights, maxcor 10) with
+    the oracle's objective, the measure and share of test_fp32_classifier_objective_statistics_match_scipy: at least
+    0.8 of the records carry SciPy's (nit, nfev, status) and its x to 1e-7."""
+    res = []
+    for family in ("four_wave_static", "run_time_layout", "queue", "twelve_waves", "eight_waves_float32"):
+        for name, pattern, tag, x0, lo, hi, opts, rec, seen in _oracle_runs(family):
+            if pattern in "abcde":
+                fg = T.oracle_fg(name, False)
+                a = minimize(lambda x: tuple(fg(x)), x0, jac=True, method="L-BFGS-B", bounds=Bounds(lo, hi), options=opts)
+                res.append((a, rec))
+    R = len(res)
+    same = sum((a.nit, a.nfev, a.status) == (b.nit, b.nfev, b.status) and np.allclose(a.x, b.x, atol=1e-7) for a, b in res)
+    print("bound patterns: %d of %d records identical to SciPy's" % (same, R))
+    assert R >= 160 and same >= 0.8 * R
+    fa, fb = np.array([a.fun for a, _ in res]), np.array([b.fun for _, b in res])
+    assert np.median(np.abs(fa - fb)) <= 1e-6
+    assert np.mean(np.abs(fa - fb) < 1e-4) >= 0.9
