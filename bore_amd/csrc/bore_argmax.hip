@@ -371,11 +371,20 @@ struct ScreenRequest {
 // The forced choices of the acquisition launches (tests, A/B): BORE_LBFGSB_COOP_GRID (unset: 2^22),
 // _WAVES, _BIG, _QUEUE, _OCC2 and BORE_SCREEN_SPLIT (unset: -1).  Read once per call, by the entry point: the plans
 // below take them, the device's CU count and the batch mode as arguments and ask nothing of their surroundings.
-struct AcqKnobs { long long coop_grid = 1LL << 22, queue = -1; int waves = -1, big = -1, occ2 = -1, screen_split = -1; };
+// BORE_LBFGSB_HELPER (the fused kernels' job board, lbfgsb_body's HELPER; unset: BORE_HELPER_DEFAULT): 0 off -- the
+// kernels without the board --, 1 on, 2 on with every speculative result dropped (exact jobs only), 3 on with helpers
+// that take nothing (every job withdrawn and run by its owner).  All four give the same bits (tests, A/B).
+#define BORE_HELPER_DEFAULT 1
+struct AcqKnobs {
+  long long coop_grid = 1LL << 22, queue = -1; int waves = -1, big = -1, occ2 = -1, screen_split = -1;
+  int helper = BORE_HELPER_DEFAULT;
+};
 static AcqKnobs acq_knobs() {
   auto env = [](const char *name, long long unset) { return getenv(name) ? atoll(getenv(name)) : unset; };
+  const int helper = (int)env("BORE_LBFGSB_HELPER", BORE_HELPER_DEFAULT);
   return AcqKnobs{env("BORE_LBFGSB_COOP_GRID", 1LL << 22), env("BORE_LBFGSB_QUEUE", -1), (int)env("BORE_LBFGSB_WAVES", -1),
-                  (int)env("BORE_LBFGSB_BIG", -1), (int)env("BORE_LBFGSB_OCC2", -1), (int)env("BORE_SCREEN_SPLIT", -1)};
+                  (int)env("BORE_LBFGSB_BIG", -1), (int)env("BORE_LBFGSB_OCC2", -1), (int)env("BORE_SCREEN_SPLIT", -1),
+                  helper >= 0 && helper <= 3 ? helper : BORE_HELPER_DEFAULT};
 }
 
 // A screening launch as planned from the request's sizes alone: no pointer is looked at.
@@ -573,9 +582,148 @@ extern "C" int bore_debug_lpp(unsigned long long *out) {  // [LB_PP_MAX][64]
 // pinned block as write-through stores, the flag after the others have been acknowledged, and the L2 keeps its
 // dirty lines: that write-back, one per loop-iteration and serialised per XCD, was what held every schedule of
 // round 4 at ~0.71 M loop-iterations per second (profiles/r5/ab_log.txt).
-template <int SHAPE, bool BF16 = false, bool LEAN = false, bool ALWAYS_COOP = false, bool MAYQ = true, int PUBLISH = 0>
+// ---- the job board of the restart phase (HELPER; lbfgsb.h: JOB BOARD) ----------------------------------------
+// A wave of the fused kernel owns one restart and walks its once-per-iteration routines one after another, while the
+// workgroup's fourth wave (three restarts) and the waves of finished restarts have nothing to do.  With HELPER those
+// waves form and factor K -- formk -- for an owner: speculatively while the owner finds its Cauchy point, or, where
+// that was not possible or the guess was wrong, while it computes its reduced gradient.
+// One slot per problem, JOB_INTS ints of LDS: state | formk's return code | col head nfree nenter ileave updatd
+// iupdat | speculative? | which block is live | - | theta (fp64 at ints 12, 13).  They live in the `vals` region of
+// the carve (BORE_BATCH_MAX floats, read by the lane-per-problem loop alone, which ALWAYS_COOP kernels do not compile);
+// the finished-problem counter is the queue's word (o_queue: these launches have no queue), the job counters follow
+// the per-problem evaluation counts.  All of it starts as the zeroed LDS begin_kernel leaves: every slot JOB_FREE.
+// A problem's wn / snd block and its 2m reciprocals rwn -- what formk writes -- have a spare set beside them
+// (a.big_wave: float offset of the spares in the workgroup's LDS, past this phase's own carve -- iteration_plan; 0:
+// none, no speculative jobs): a speculative job copies the live block to the other set and works there, and its owner
+// makes that set the live one if the guess was right.  (rwn too: an iteration without a free variable calls no formk,
+// and the next may run subsm on the factor it finds -- a dropped job must leave no trace.)
+//
+// Why nobody can wait for ever.  An owner waits only for a job whose state it has SEEN to be TAKEN (its own
+// compare-and-swap POSTED -> WITHDRAWN failed, and nobody but a helper moves a slot out of POSTED).  The helper that
+// took it is then copying the block, inside formk, or between formk and its DONE store: straight-line code over LDS
+// with finite loops and no wait on any other wave.  So every wait is for a wave that itself waits for nothing.  A
+// helper never waits: it polls the slots and the finished counter and sleeps in between, and leaves once every owner
+// has finished -- an owner counts itself finished after lbfgsb_advance has returned, and every path through an
+// iteration that posts a job withdraws it or waits for it (post / collect / drop), so no POSTED or TAKEN slot is left
+// then.  A job no helper has taken when its owner needs the result is withdrawn and run by the owner, as without the board.
+enum { JOB_FREE = 0, JOB_POSTED = 1, JOB_TAKEN = 2, JOB_DONE = 3, JOB_WITHDRAWN = 4, JOB_INTS = 16 };
+// (job counters, summed into g_helper_stats by the wave that publishes the loop's pick.  speculative = committed +
+// dropped + those withdrawn with a right guess; exact jobs are taken or withdrawn)
+enum { JOBS_SPECULATIVE = 0, JOBS_COMMITTED, JOBS_DROPPED, JOBS_TAKEN, JOBS_WITHDRAWN, JOBS_COUNTERS };
+__device__ unsigned long long g_helper_stats[JOBS_COUNTERS];
+// Diagnostic (not part of include/bore_hip.h; beside bore_debug_engine_loop_stats): the device's sums of jobs posted
+// speculatively, committed, dropped, taken exact and withdrawn since the last reset, over every engine of the process
+// (the pick's layout has no room for them: a device array instead of per-engine sums -- callers reset between runs).
+// To be called between runs: the copies wait for the device, as any synchronous copy does.
+extern "C" int bore_debug_helper_stats(long long *out, int reset) {
+  static const unsigned long long zero[JOBS_COUNTERS] = {0};
+  if (out) HIP_TRY(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_helper_stats), sizeof(zero)));
+  if (reset) HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_helper_stats), zero, sizeof(zero)));
+  return 0;
+}
+struct RestartJobs {
+  int *slot;              // this problem's slot
+  int *stats;             // the workgroup's job counters
+  lbfgsb::Work *wk;       // the owner's views: a committed speculative job repoints snd / wn
+  double *blk0, *blk1;    // the problem's own wn / snd block and its spare (nullptr: no speculative jobs)
+  double *rwn0, *rwn1;    // ... and the reciprocals that go with each
+  int lane, mode;         // mode: BORE_LBFGSB_HELPER's value, 0 = formk where it has always been
+  int live = 0;           // which of the two blocks wk->snd points to
+  int pending = 0;        // a speculative job is out; guess_nfree: what it assumed
+  int guess_nfree = 0;
+  int how = 0;            // set by post: 0 the exact job is out, 1 the speculative one stands, 2 it is wrong and TAKEN
+  __device__ __forceinline__ void count(int which) const {
+    if (lane == 0) __hip_atomic_fetch_add(stats + which, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  }
+  __device__ __forceinline__ void put(const lbfgsb::IterArgs &ia, int speculative) const {
+    if (lane == 0) {
+      slot[2] = ia.col; slot[3] = ia.head; slot[4] = ia.nfree; slot[5] = ia.nenter; slot[6] = ia.ileave;
+      slot[7] = ia.updatd; slot[8] = ia.iupdat; slot[9] = speculative; slot[10] = live;
+      *reinterpret_cast<double *>(slot + 12) = ia.theta;
+      // (release: the sets, the corrections and everything before them are in LDS before the state says so)
+      __hip_atomic_store(slot, (int)JOB_POSTED, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+  }
+  __device__ __forceinline__ bool withdraw() const {  // POSTED -> WITHDRAWN; false: a helper has it
+    int ok = 0;
+    if (lane == 0) {
+      int seen = JOB_POSTED;
+      ok = __hip_atomic_compare_exchange_strong(slot, &seen, (int)JOB_WITHDRAWN, __ATOMIC_ACQ_REL, __ATOMIC_ACQUIRE,
+                                                __HIP_MEMORY_SCOPE_WORKGROUP) ? 1 : 0;
+    }
+    return __builtin_amdgcn_readfirstlane(ok) != 0;
+  }
+  __device__ __forceinline__ int wait_done() const {  // TAKEN (seen by withdraw): the helper waits for nothing -- see above
+    while (__builtin_amdgcn_readfirstlane(__hip_atomic_load(slot, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)) != JOB_DONE)
+      __builtin_amdgcn_s_sleep(1);
+    return __builtin_amdgcn_readfirstlane(slot[1]);
+  }
+  __device__ __forceinline__ void speculate(const lbfgsb::IterArgs &guess, const lbfgsb::Work &) {
+    if (!mode || !blk1) return;
+    put(guess, 1);
+    pending = 1;
+    guess_nfree = guess.nfree;
+    count(JOBS_SPECULATIVE);
+  }
+  __device__ __forceinline__ void drop() {
+    if (!pending) return;
+    if (!withdraw()) (void)wait_done();
+    pending = 0;
+    count(JOBS_DROPPED);
+  }
+  __device__ __forceinline__ void post(const lbfgsb::IterArgs &ia, const lbfgsb::Work &) {
+    if (!mode) return;
+    how = 0;
+    if (pending) {
+      // (BORE_LBFGSB_HELPER = 2: every speculative result is dropped)
+      if (mode != 2 && ia.nenter == 0 && ia.ileave == ia.n + 1 && ia.nfree == guess_nfree) {
+        how = 1;
+        return;
+      }
+      if (!withdraw()) {  // wrong and running: it writes the spare block and rwn -- let it finish beside cmprlb
+        how = 2;
+        return;
+      }
+      pending = 0;
+      count(JOBS_DROPPED);
+    }
+    put(ia, 0);
+  }
+  __device__ __forceinline__ int collect(const lbfgsb::IterArgs &ia, const lbfgsb::Work &w) {
+    if (!mode) return lbfgsb::formk(ia, w);
+    if (how == 2) {
+      (void)wait_done();
+      pending = 0;
+      count(JOBS_DROPPED);
+      return lbfgsb::formk(ia, w);
+    }
+    if (withdraw()) {  // nobody took it (a right guess included: ia is the guess): formk here, on the live block
+      pending = 0;
+      count(JOBS_WITHDRAWN);
+      return lbfgsb::formk(ia, w);
+    }
+    const int rc = wait_done();
+    if (how == 1) {
+      live ^= 1;
+      wk->snd = live ? blk1 : blk0;
+      wk->wn = wk->snd + 2 * ia.m;
+      wk->rwn = live ? rwn1 : rwn0;
+      pending = 0;
+      count(JOBS_COMMITTED);
+    } else {
+      count(JOBS_TAKEN);
+    }
+    return rc;
+  }
+};
+
+// HELPER: the job board above (float32 static shape 1, one problem per wave, at most four problems per workgroup;
+// a.queue -- which MAYQ = false kernels never read as a queue -- carries BORE_LBFGSB_HELPER's value: 1, 2 or 3).
+template <int SHAPE, bool BF16 = false, bool LEAN = false, bool ALWAYS_COOP = false, bool MAYQ = true, int PUBLISH = 0,
+          bool HELPER = false>
 __device__ __forceinline__ void lbfgsb_body(const LbfgsbArgs &a, const long long model,
                                             const int block_y, const int it_now = -1) {
+  static_assert(!HELPER || (SHAPE == 1 && !BF16 && ALWAYS_COOP && !MAYQ), "the job board: the fused float32 kernels of shape 1");
   extern __shared__ float smem[];
   constexpr MlpLayout Lc = bore_static_layout(SHAPE > 0 ? SHAPE : 0, 2, BORE_BATCH_MAX);
   const long long c_enter = BORE_LCLOCK();
@@ -654,10 +802,18 @@ __device__ __forceinline__ void lbfgsb_body(const LbfgsbArgs &a, const long long
     my_big = a.big + ((size_t)big_slot * 8 + wv) * (size_t)a.big_wave;
   }
   const long long c_staged = BORE_LCLOCK();
+  // (the job board: one problem per wave in four slots; 5..16 restarts take turns on the waves and keep the serial form)
+  const bool helping = HELPER && np <= 4 && a.queue != 0;
+  int *const job_slots = reinterpret_cast<int *>(vals);
+  double *const spares = HELPER && a.big_wave > 0 ? reinterpret_cast<double *>(smem + a.big_wave) : nullptr;
   if (wv >= np) {  // wave without problems (np < 4)
+    if constexpr (HELPER) {
+      if (!helping) return;  // (otherwise: on to the helper loop at the end; the pass loop below ends at once for it)
+    } else {
     if (use_big && lane == 0 && atomicAdd(qnext + 2, 1) == NW - 1)
       __hip_atomic_store(a.big_locks + big_slot, 0, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
     return;
+    }
   }
   double *res = reinterpret_cast<double *>(smem + a.o_res);  // batch mode: [np][D + 3] fun, status, nfev, x
   int *cnt = reinterpret_cast<int *>(res + (multi ? np : 4) * (D + 3));
@@ -853,7 +1009,17 @@ __device__ __forceinline__ void lbfgsb_body(const LbfgsbArgs &a, const long long
           t_fg += BORE_LCLOCK() - c1;
           ++n_rounds;
         };
+        if constexpr (HELPER) {
+          const int nb = lbfgsb::big_size(a.opt.m);
+          double *const spare = spares ? spares + (size_t)myp * (nb + 2 * a.opt.m) : nullptr;
+          const RestartJobs jobs{job_slots + myp * JOB_INTS, execs + 4, &wk, wk.snd, spare, wk.rwn,
+                                 spare ? spare + nb : nullptr, lane, helping ? a.queue : 0};
+          lbfgsb::lbfgsb_advance<SHAPE != 1>(st, wk, blo, bhi, bnbd, a.opt, cp, evaluate, evaluate2, jobs);
+          // (this problem posts nothing any more: the helpers leave when every problem of the workgroup has said so)
+          if (helping && lane == 0) __hip_atomic_fetch_add(qnext, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+        } else {
         lbfgsb::lbfgsb_advance<SHAPE != 1>(st, wk, blo, bhi, bnbd, a.opt, cp, evaluate, evaluate2);
+        }
       } else {
         lbfgsb::lbfgsb_advance<SHAPE != 1>(st, wk, blo, bhi, bnbd, a.opt, cp, evaluate);
       }
@@ -1056,6 +1222,11 @@ __device__ __forceinline__ void lbfgsb_body(const LbfgsbArgs &a, const long long
       for (int i = 3; i < 7; ++i) put(D + i, 0.0);
     }
     put(D + 7, exec_sum);  // evaluations that ran the network (<= nfev_sum: the image shortcut serves the rest)
+    if constexpr (HELPER) {  // (every owner's counts are in: this wave is the last to finish)
+      for (int c = 0; c < JOBS_COUNTERS; ++c)
+        if (const int v = execs[4 + c])
+          __hip_atomic_fetch_add(g_helper_stats + c, (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     if constexpr (PUBLISH == 1) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (this lane's stores -- the pick above among them -- are acknowledged)
       // (an exchange, not a store: the wave waits for it to have happened.  As a plain write-through store the flag
@@ -1078,6 +1249,64 @@ __device__ __forceinline__ void lbfgsb_body(const LbfgsbArgs &a, const long long
     }
   }
   }  // passes
+  if constexpr (HELPER) {
+    // ---- the helper loop: a wave that never had a problem, or whose problem is finished (and reported) ----
+    // (BORE_LBFGSB_HELPER = 3: the helpers take nothing -- every job is withdrawn and run by its owner)
+    const bool take = a.queue != 3;
+    while (helping) {
+      int took = -1;
+      if (lane == 0 && take)
+        for (int j = 0; j < np; ++j) {
+          int *sl = job_slots + j * JOB_INTS;
+          if (__hip_atomic_load(sl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != JOB_POSTED) continue;
+          int seen = JOB_POSTED;
+          if (__hip_atomic_compare_exchange_strong(sl, &seen, (int)JOB_TAKEN, __ATOMIC_ACQUIRE, __ATOMIC_RELAXED,
+                                                   __HIP_MEMORY_SCOPE_WORKGROUP)) {
+            took = j;
+            break;
+          }
+        }
+      took = __builtin_amdgcn_readfirstlane(took);
+      if (took >= 0) {
+        // the owner's problem, from the slot number alone: its workspace, the scalars it posted, this wave's lanes
+        int *sl = job_slots + took * JOB_INTS;
+        float *base = smem + a.o_prob + (size_t)took * a.prob_floats;
+        lbfgsb::Work w = lbfgsb::make_work(reinterpret_cast<double *>(base + a.o_dw),
+                                           reinterpret_cast<int *>(base + a.o_iw), D, a.opt.m, nullptr);
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");  // (lane 0 took the job for all lanes)
+        {
+          // which set: the live one, or -- speculative -- the other one with a copy of the live block (pairs: 16-byte
+          // moves; formk writes every reciprocal it or subsm reads)
+          const int speculative = uniform_i32(sl[9]), live = uniform_i32(sl[10]), nb = lbfgsb::big_size(a.opt.m);
+          double *b0 = w.snd, *b1 = spares ? spares + (size_t)took * (nb + 2 * a.opt.m) : b0;  // (no spares: neither flag is ever set)
+          double *src = live ? b1 : b0, *dst = speculative ? (live ? b0 : b1) : src;
+          if (dst != b0) w.rwn = b1 + nb;
+          if (speculative) {
+            for (int i = 2 * lane; i < nb; i += 128) {
+              const double v0 = src[i], v1 = src[i + 1];
+              dst[i] = v0;
+              dst[i + 1] = v1;
+            }
+            wave_lds_sync();
+          }
+          w.snd = dst;
+          w.wn = dst + 2 * a.opt.m;
+        }
+        const lbfgsb::IterArgs ia{D, a.opt.m, uniform_i32(sl[2]), uniform_i32(sl[3]), uniform_i32(sl[4]),
+                                  uniform_i32(sl[5]), uniform_i32(sl[6]), uniform_i32(sl[7]), uniform_i32(sl[8]),
+                                  *reinterpret_cast<const double *>(sl + 12), 0.0, lbfgsb::Coop{lane, 64}};
+        const int rc = lbfgsb::formk(ia, w);
+        wave_lds_sync();  // (every lane's entries of the factor are in LDS)
+        if (lane == 0) {
+          sl[1] = rc;
+          __hip_atomic_store(sl, (int)JOB_DONE, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+        continue;
+      }
+      if (uniform_i32(__hip_atomic_load(qnext, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) >= np) break;
+      __builtin_amdgcn_s_sleep(4);
+    }
+  }
   if (use_big) {  // the workgroup's last wave to get here frees the pool slot
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (lane == 0 && atomicAdd(qnext + 2, 1) == NW - 1)

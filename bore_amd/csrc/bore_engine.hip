@@ -442,6 +442,7 @@ int async_create(bore_engine *e, const double *X0, const double *y0) {
     E.gamma = c.gamma; E.epochs = c.epochs; E.batch_size = c.batch_size; E.seed = c.seed; E.loop_id0 = c.loop_id0;
     E.adam = &c.adam; E.num_samples = c.num_samples; E.low = e->low.data(); E.high = e->high.data();
     E.num_starts = c.num_starts; E.transform = c.transform; E.opts = &c.lbfgsb; E.n_loops = c.n_loops;
+    E.helper = acq_knobs().helper;  // (BORE_LBFGSB_HELPER: read here, once per engine)
   }
   std::vector<float> x32(L * n0 * D);
   for (size_t i = 0; i < x32.size(); ++i) x32[i] = (float)X0[i];

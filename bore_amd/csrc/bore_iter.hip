@@ -94,7 +94,7 @@ __device__ __forceinline__ void phase_handoff() {
 }
 
 // LOCAL: everything this loop's state has been through stayed on this XCD (see lbfgsb_body's PUBLISH).
-template <int SHAPE, bool LOCAL = false>
+template <int SHAPE, bool LOCAL = false, bool HELPER = false>
 __device__ __forceinline__ void iteration_once(const IterArgs *__restrict__ pa,
                                                          const long long slot, const int it,
                                                          const bool staged, const long long t_begin = 0) {
@@ -141,7 +141,7 @@ __device__ __forceinline__ void iteration_once(const IterArgs *__restrict__ pa,
     __threadfence();
     __syncthreads();
   }
-  lbfgsb_body<SHAPE, false, true, true, false, LOCAL ? 1 : 0>(a.b, slot, 0, it);  // (publishes flag[lid] = it + 1)
+  lbfgsb_body<SHAPE, false, true, true, false, LOCAL ? 1 : 0, HELPER>(a.b, slot, 0, it);  // (publishes flag[lid] = it + 1)
 }
 
 // RESIDENT: the workgroup may go on to later iterations of its loop.  Otherwise ONE iteration -- the
@@ -151,7 +151,9 @@ __device__ __forceinline__ void iteration_once(const IterArgs *__restrict__ pa,
 // registers, no scratch) -- the kernel for up to 2 x CUs loops.  3: 168 registers, the restart phase pays with spills
 // to scratch (its per-loop time +7 %), and a CU runs three loops: the kernel for more loops than that (round 5;
 // 768 loops 549 -> 606 k it/s).
-template <int SHAPE, bool RESIDENT, int OCC = 2>
+// HELPER: idle waves of the restart phase form and factor K for the busy ones (bore_argmax.hip, the job board) -- a
+// kernel of its own beside the one without, which BORE_LBFGSB_HELPER = 0 and launches it does not cover keep.
+template <int SHAPE, bool RESIDENT, int OCC = 2, bool HELPER = false>
 __global__ __launch_bounds__(BORE_THREADS, OCC) void iteration_kernel(const IterArgs *__restrict__ pa) {
   const long long slot = blockIdx.x;
   const int it_first = uniform_i32(pa->f.its[slot]);
@@ -185,7 +187,7 @@ __global__ __launch_bounds__(BORE_THREADS, OCC) void iteration_kernel(const Iter
     if (stp && threadIdx.x == 0) stp[3] = wall_clock64();
     __threadfence();
     __syncthreads();
-    lbfgsb_body<SHAPE, false, true, true, false>(a.b, slot, 0);  // (publishes flag[lid] = it + 1)
+    lbfgsb_body<SHAPE, false, true, true, false, 0, HELPER>(a.b, slot, 0);  // (publishes flag[lid] = it + 1)
     // not the loop's last iteration: leave the next one to a later launch.  (Any wave may say so,
     // and before the others are done: the host reacts to `parked` only after the flag.)
     if (a.targets && threadIdx.x == 0 && it + 1 < a.targets[slot])
@@ -223,7 +225,7 @@ __global__ __launch_bounds__(BORE_THREADS, OCC) void iteration_kernel(const Iter
     asm volatile("" : "+s"(pa_bits));
     typedef const __attribute__((address_space(4))) IterArgs *IterArgsConst;
     // (LOCAL: workgroup-scope hand-overs; rounds 2 - 4's agent / system-scope fences lost the A/B, profiles/r5/ab_log.txt)
-    iteration_once<SHAPE, true>((const IterArgs *)(IterArgsConst)pa_bits, slot, it, it == it_first);
+    iteration_once<SHAPE, true, HELPER>((const IterArgs *)(IterArgsConst)pa_bits, slot, it, it == it_first);
     __syncthreads();  // the waves leave the restart phase one by one: LDS is reused below
     ++it;
     if (threadIdx.x == 0) __hip_atomic_fetch_add(prog, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -287,7 +289,7 @@ extern "C" int bore_debug_wg_starts(long long *out) {
   return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wg_start), sizeof(long long) * 4096 * 2);
 }
 #endif
-template <int SHAPE, int OCC = 2>
+template <int SHAPE, int OCC = 2, bool HELPER = false>
 __global__ __launch_bounds__(BORE_THREADS, OCC) void queue_kernel(const IterArgs *__restrict__ pa) {
   __shared__ __attribute__((aligned(16))) int s_q4[4];  // (16 B: the dynamic LDS keeps its alignment)
 #ifdef BORE_QUEUE_STAMP_DRAW
@@ -372,7 +374,7 @@ __global__ __launch_bounds__(BORE_THREADS, OCC) void queue_kernel(const IterArgs
     unsigned long long pa_bits = reinterpret_cast<unsigned long long>(pa);
     asm volatile("" : "+s"(pa_bits));
     typedef const __attribute__((address_space(4))) IterArgs *IterArgsConst;
-    iteration_once<SHAPE>((const IterArgs *)(IterArgsConst)pa_bits, (long long)lid, it, false, t_begin);
+    iteration_once<SHAPE, false, HELPER>((const IterArgs *)(IterArgsConst)pa_bits, (long long)lid, it, false, t_begin);
     __syncthreads();  // the waves leave the restart phase one by one: LDS is reused by the next iteration
   }
 }
@@ -447,6 +449,7 @@ struct IterEngine {
   int num_starts, transform;
   const bore_lbfgsb_opts *opts;
   int n_loops;  // L: the slots a worker's staging block is laid out for
+  int helper;   // AcqKnobs::helper as the environment had it when the engine was created
 };
 
 // A WORKER of the asynchronous engine (bore_engine.hip) is a stream that runs one launch -- the fused kernel, or the
@@ -478,6 +481,9 @@ struct IterPlan {
   int shape;
   size_t lds_bytes;      // dynamic LDS per loop: the largest of the phases'
   size_t part_bytes[4];  // fit, screen, restarts, labels (BORE_ASYNC_DEBUG's line)
+  // BORE_LBFGSB_HELPER's value where the job board applies (float32 shape 1, at most four restarts: one per wave; the
+  // two-loops-per-CU kernels -- the launches say which), else 0
+  int helper;
 };
 
 // What a fused launch of `n_slots` loops of the batch currently set (bore_set_batch) on worker w needs: fills the
@@ -528,10 +534,27 @@ static int iteration_plan(const IterEngine &E, const Worker &w, int n_slots, Ite
   floats = floats > lb ? floats : lb;
   const size_t labels_floats = 2 * ((size_t)cap + 2);
   floats = floats > labels_floats ? floats : labels_floats;
-  *plan = IterPlan{shape, floats * 4, {lf * 4, ls * 4, lb * 4, labels_floats * 4}};
+  const int helper = shape == 1 && E.num_starts <= 4 ? E.helper : 0;
+  // (the restart phase of a fused launch has no queue and no pool: the helper kernels read the board's mode from the
+  // one word, and from the other where the spare wn / snd blocks of the speculative jobs start -- float offset, 0: none.
+  // The launches below clear both again for the kernels without the board: fused_without_board)
+  h->b.queue = helper;
+  if (helper) {
+    // One spare wn / snd block and its 2m reciprocals per restart, past the restart phase's own carve (lbfgsb_plan's
+    // stays as it is).  The fit phase needs more LDS than the restarts: the spares lie in what the kernel has anyway.
+    // Where they do not (a large maxcor), the launch is NOT grown -- its size, and with it the loops per CU of every
+    // kernel of the plan, stays what it was -- and the board runs exact jobs only.
+    const size_t at = (lb + 3) & ~(size_t)3, need = 2 * ((size_t)lbfgsb::big_size(E.opts->maxcor) + 2 * (size_t)E.opts->maxcor) * E.num_starts;
+    h->b.big_wave = at + need <= floats ? (int)at : 0;
+  }
+  *plan = IterPlan{shape, floats * 4, {lf * 4, ls * 4, lb * 4, labels_floats * 4}, helper};
   // (every kernel the shape may be launched with, up front)
   return bore_with_flavour<fused_flavour_on>(FusedFlavours{}, shape, [&](auto S) {
     int rc = 0;
+    if constexpr (S() == 1)
+      if ((rc = allow_lds(iteration_kernel<1, true, 2, true>, floats * 4)) || (rc = allow_lds(iteration_kernel<1, false, 2, true>, floats * 4)) ||
+          (rc = allow_lds(queue_kernel<1, 2, true>, floats * 4)))
+        return rc;
     if ((rc = allow_lds(iteration_kernel<S(), true, 2>, floats * 4)) || (rc = allow_lds(iteration_kernel<S(), false, 2>, floats * 4)) ||
         (rc = allow_lds(queue_kernel<S(), 2>, floats * 4)))
       return rc;
@@ -548,6 +571,14 @@ static int fused_launch(K kernel, int workgroups, const IterPlan &p, const Worke
   return 0;
 }
 
+// A launch that takes a kernel without the job board (three loops per CU): the plan's board words go back to what
+// LbfgsbArgs means by them everywhere else -- no queue, no pool.
+static void fused_without_board(IterArgs *h, IterPlan &p) {
+  p.helper = 0;
+  h->b.queue = 0;
+  h->b.big_wave = 0;
+}
+
 // The work-queue launch on worker w: a fixed grid of q.wgs workgroups, fed by the host through q.ring.  Only the
 // arguments are uploaded (ids[] is the identity, the rows come through ynew).
 static int iteration_launch_queue(const IterEngine &E, Worker &w, int n_slots, const IterQueue &q) {
@@ -559,11 +590,14 @@ static int iteration_launch_queue(const IterEngine &E, Worker &w, int n_slots, c
   h->q_ring = q.ring; h->q_head = q.head; h->q_mask = q.mask; h->q_tail_host = q.tail_host;
   h->targets = nullptr;
   h->wait_ticks = 0;
+  if (fused_most_per_cu(p.shape) == 3 && q.wgs > 2 * device_cus()) fused_without_board(h, p);
   HIP_TRY(hipMemcpyAsync(w.d_args, h, sizeof(IterArgs), hipMemcpyHostToDevice, w.stream));
   return bore_with_flavour<fused_flavour_on>(FusedFlavours{}, p.shape, [&](auto S) {
     // (no more workgroups than two per CU: the kernel with the whole register file)
     if constexpr (fused_most_per_cu(S()) == 3)
       if (q.wgs > 2 * device_cus()) return fused_launch(queue_kernel<S(), 3>, q.wgs, p, w);
+    if constexpr (S() == 1)
+      if (p.helper) return fused_launch(queue_kernel<1, 2, true>, q.wgs, p, w);
     return fused_launch(queue_kernel<S(), 2>, q.wgs, p, w);
   });
 }
@@ -584,10 +618,16 @@ static int iteration_launch(const IterEngine &E, Worker &w, int n_slots) {
               p.lds_bytes, p.part_bytes[0], p.part_bytes[1], p.part_bytes[2], p.part_bytes[3], per_cu);
     if (g_batch->resident_loops > per_cu * device_cus()) h->wait_ticks = 0;
   }
+  if (fused_most_per_cu(p.shape) == 3 && h->wait_ticks > 0 && g_batch->resident_loops > 2 * device_cus()) fused_without_board(h, p);
   HIP_TRY(hipMemcpyAsync(w.d_args, h, w.stage_bytes, hipMemcpyHostToDevice, w.stream));
   return bore_with_flavour<fused_flavour_on>(FusedFlavours{}, p.shape, [&](auto S) {
     if constexpr (fused_most_per_cu(S()) == 3)  // (three loops per CU: see iteration_kernel)
       if (h->wait_ticks > 0 && g_batch->resident_loops > 2 * device_cus()) return fused_launch(iteration_kernel<S(), true, 3>, n_slots, p, w);
+    if constexpr (S() == 1)
+      if (p.helper) {
+        if (h->wait_ticks > 0) return fused_launch(iteration_kernel<1, true, 2, true>, n_slots, p, w);
+        return fused_launch(iteration_kernel<1, false, 2, true>, n_slots, p, w);
+      }
     if (h->wait_ticks > 0) return fused_launch(iteration_kernel<S(), true, 2>, n_slots, p, w);
     return fused_launch(iteration_kernel<S(), false, 2>, n_slots, p, w);
   });

@@ -1861,14 +1861,36 @@ LB_HD void lbfgsb_init(State &s, const Work &w, int n, int m, const double *x0, 
 // search (step bound, saves) keeps the workspace form; the registers go back to the workspace when
 // the search ends.  Same operations on the same values in the same order: same bits (tested against
 // the other two forms on the host, tests/test_lbfgsb_host.py, and on the device).
+//
+// JOB BOARD (DIRECT callers may add `jobs`): formk reads ws, wy, sy, theta and the index sets and writes wn / snd /
+// rwn; cmprlb reads and writes none of these but ws, wy and the index (read only).  So once freev has fixed the
+// sets, somebody else may form and factor K while this caller computes the reduced gradient:
+//   jobs.post(ia, w)     -- formk(ia, w) may start NOW, anywhere (the sets, ws, wy, sy stay as they are until collect);
+//   jobs.collect(ia, w)  -- formk(ia, w)'s return code, with wn / snd / rwn as that call leaves them: run by whoever
+//                           took the job, or by this caller inside collect when nobody did.
+// And cauchy and freev touch none of formk's operands either, while on an interior iteration freev leaves the sets
+// as the previous iteration had them.  So at the top of an iteration that follows a BFGS update:
+//   jobs.speculate(guess, w) -- formk(guess, .) may start NOW on a COPY of the wn / snd block and another rwn (formk
+//                           updates snd in place, and an iteration that ends up calling no formk leaves the old
+//                           factor to a later subsm: a wrong guess must leave no trace); guess = ia with nothing
+//                           entering or leaving.
+//   post() then compares its ia with the guess: alike (nfree, nenter == 0, ileave == n + 1) -- collect() makes the
+//   copy the live block (the board may repoint w.snd / w.wn / w.rwn); else the speculative result is dropped and the exact job
+//   takes its place.  jobs.drop(): the iteration calls no formk after all (cauchy failed, no free variable).
+// formk's failure is tested before cmprlb's, as in the serial order.  A routine's arithmetic does not depend on who
+// runs it, or when, as long as its operands are those of the serial order: the same bits (the device's board:
+// bore_argmax.hip, RestartJobs; tests/native/restart_helper_host.cpp checks the rule on the host, which stays serial).
 struct ReverseCommunication {};
 struct NoTwoVariableForm {};
-template <bool VL = true, class FG = ReverseCommunication, class FG2 = NoTwoVariableForm>
+struct NoJobBoard {};
+template <bool VL = true, class FG = ReverseCommunication, class FG2 = NoTwoVariableForm, class JB = NoJobBoard>
 LB_HD int lbfgsb_advance(State &s, const Work &w, const double *l, const double *u,
                          const int *nbd, const Options &opt, const Coop coop_in = Coop{0, 1},
-                         FG fg = FG{}, FG2 fg2 = FG2{}) {
+                         FG fg = FG{}, FG2 fg2 = FG2{}, JB jobs = JB{}) {
   constexpr bool DIRECT = !std::is_same<FG, ReverseCommunication>::value;
   constexpr bool TWO = DIRECT && !std::is_same<FG2, NoTwoVariableForm>::value;
+  constexpr bool JOBS = DIRECT && !std::is_same<JB, NoJobBoard>::value;
+  (void)jobs;
   Coop coop = coop_in;
   const int n = LB_UNI(s.n, coop_in), m = LB_UNI(s.m, coop_in);
   bool first_ls = false;
@@ -2024,12 +2046,23 @@ LB_HD int lbfgsb_advance(State &s, const Work &w, const double *l, const double 
         const IterArgs ia{n, m, LB_UNI(s.col, coop), LB_UNI(s.head, coop), LB_UNI(s.nfree, coop),
                           LB_UNI(s.nenter, coop), LB_UNI(s.ileave, coop), LB_UNI(s.updatd, coop),
                           LB_UNI(s.iupdat, coop), s.theta, s.sbgnrm, coop};
+        if constexpr (JOBS) {
+          // (the previous iteration ended with a BFGS update: formk will run, and on an interior iteration with the
+          // sets as they stand -- the prediction, checked by post())
+          if (ia.updatd && ia.col > 0 && ia.nfree > 0) {
+            IterArgs guess = ia;
+            guess.nenter = 0;
+            guess.ileave = n + 1;
+            jobs.speculate(guess, w);
+          }
+        }
         LB_PHASE_BEGIN(21);
         const int rc = cauchy<VL>(ia, w, l, u, nbd);
         LB_PHASE_END(0);
         s.nseg = rc >> 8;
         if (rc & 0xff) {  // singular triangular system: refresh the memory
           LB_EVENT(s, EV_CAUCHY_SINGULAR_REFRESH);
+          if constexpr (JOBS) jobs.drop();
           refresh_memory(s);
           continue;
         }
@@ -2047,7 +2080,30 @@ LB_HD int lbfgsb_advance(State &s, const Work &w, const double *l, const double 
         const IterArgs ia{n, m, LB_UNI(s.col, coop), LB_UNI(s.head, coop), LB_UNI(s.nfree, coop),
                           LB_UNI(s.nenter, coop), LB_UNI(s.ileave, coop), LB_UNI(s.updatd, coop),
                           LB_UNI(s.iupdat, coop), s.theta, s.sbgnrm, coop};
-        if (s.wrk) {
+        if constexpr (JOBS) {
+          const bool wrk = s.wrk != 0;
+          if (wrk) {
+            LB_PHASE_BEGIN(23);
+            if (big_stale) {
+              zero_big(w, m, coop);
+              big_stale = false;
+            }
+            jobs.post(ia, w);
+            LB_PHASE_END(1);
+          } else {
+            jobs.drop();
+          }
+          LB_PHASE_BEGIN(24);
+          const int cm = cmprlb(s, w, coop);
+          LB_PHASE_END(2);
+          if (wrk) {
+            LB_PHASE_BEGIN(23);
+            const int fk = jobs.collect(ia, w);
+            LB_PHASE_END(1);
+            if (fk) { LB_EVENT(s, EV_FORMK_REFRESH); refresh_memory(s); continue; }
+          }
+          if (cm) { LB_EVENT(s, EV_CMPRLB_REFRESH); refresh_memory(s); continue; }
+        } else if (s.wrk) {
           LB_PHASE_BEGIN(23);
           if (DIRECT && big_stale) {
             zero_big(w, m, coop);
@@ -2058,7 +2114,7 @@ LB_HD int lbfgsb_advance(State &s, const Work &w, const double *l, const double 
           if (fk) { LB_EVENT(s, EV_FORMK_REFRESH); refresh_memory(s); continue; }
         }
         int rc;
-        {
+        if constexpr (!JOBS) {
           LB_PHASE_BEGIN(24);
           const int cm = cmprlb(s, w, coop);
           LB_PHASE_END(2);
@@ -2072,6 +2128,8 @@ LB_HD int lbfgsb_advance(State &s, const Work &w, const double *l, const double 
         s.iword = rc >> 8;
         if (rc & 0xff) { LB_EVENT(s, EV_SUBSM_REFRESH); refresh_memory(s); continue; }
         if (s.iword == 1) LB_EVENT(s, EV_SUBSM_HIT_BOUND);
+      } else {
+        if constexpr (JOBS) jobs.drop();  // (no subspace minimisation: a speculative job is not wanted)
       }
       {
         LB_PHASE_BEGIN(26);
