@@ -888,9 +888,13 @@ __device__ __forceinline__ void wide_rounds_f32(const Net &net, const float (&xi
 }
 
 // (the body is a device function so that the fused iteration kernel of bore_iter.hip can run it)
-template <int SHAPE, int NW = 4>
+// WEIGHTED (the generic flavour alone, never batch mode): `sw` holds a sample weight per row, [n_models][N] like z; row
+// i's loss term and d loss / d logit are scaled by sw[i], the divisor of the batch mean stays the row count.  A
+// template flag, so that every other instantiation is the code it was.
+template <int SHAPE, int NW = 4, bool WEIGHTED = false>
 __device__ __forceinline__ void fit_body(const FitArgs &a, const long long slot,
-                                         const int it_now = -1) {
+                                         const int it_now = -1, const float *sw = nullptr) {
+  static_assert(!WEIGHTED || (SHAPE == 0 && NW == 4), "sample weights: the generic four-wave flavour");
   extern __shared__ float smem[];
   constexpr MlpLayout Lc = bore_static_layout(SHAPE > 0 ? SHAPE : 0, 1, BORE_BATCH_MAX);
   constexpr bool WIDE = bore_shape_is_wide(SHAPE > 0 ? SHAPE : 0);
@@ -926,6 +930,7 @@ __device__ __forceinline__ void fit_body(const FitArgs &a, const long long slot,
   float *v_g = a.av + model * P;
   const float *X_g = a.X + model * (a.ids ? a.cap : (long long)N) * D;
   const float *z_g = a.z + model * (a.ids ? a.cap : (long long)N);
+  [[maybe_unused]] const float *sw_g = WEIGHTED ? sw + model * (long long)N : nullptr;
   float *sm = smem + a.o_m, *sv = smem + a.o_v;  // padded images (when state_in_lds)
   float *gacc = smem + a.o_g;  // weight-gradient sums carried between sub-tiles (batch_size > 64)
 
@@ -1191,6 +1196,7 @@ __device__ __forceinline__ void fit_body(const FitArgs &a, const long long slot,
           FIT_MARK(3);
           BORE_WSTAMP(4);
         } else {
+        [[maybe_unused]] float wrow = 0.f;  // (WEIGHTED) the sample weight of row rb * 16 + m16, from memory
         {  // gather the mini-batch rows of this row-block (rows past the sub-tile: zeros)
           float *A0 = tile + L.aoff[0] + (rb * 16 + m16) * L.lda[0];
           const int row = rb * 16 + m16;
@@ -1206,6 +1212,8 @@ __device__ __forceinline__ void fit_body(const FitArgs &a, const long long slot,
             for (int d = q4; d < D; d += 4) A0[d] = row < nr ? X_g[src * D + d] : 0.f;
             if (q4 == 0) zt[row] = row < nr ? z_g[src] : 0.f;
           }
+          // (requested here, used after the forward pass; lanes 0..15 -- m16 == lane -- are the ones that use it)
+          if constexpr (WEIGHTED) wrow = row < nr ? sw_g[src] : 0.f;
         }
         wave_lds_sync();
         fwd_all<true>(L, n, th, tile, rb, /*keep_logits=*/true);
@@ -1215,7 +1223,9 @@ __device__ __forceinline__ void fit_body(const FitArgs &a, const long long slot,
           if (row < nr) {
             const float x = tile[L.aoff[n] + row * L.lda[n]];
             const float zz = zt[row];
-            delta = fit_bce(x, zz, a.epoch_loss != nullptr, eloss) * inv_nb;  // (eloss: per lane, reduced once per epoch)
+            // (eloss: per lane, reduced once per epoch)
+            if constexpr (WEIGHTED) delta = (fit_bce_weighted(x, zz, wrow, a.epoch_loss != nullptr, eloss) * inv_nb) * wrow;
+            else delta = fit_bce(x, zz, a.epoch_loss != nullptr, eloss) * inv_nb;
           }
           tile[L.doff[n] + row * L.lda[n]] = delta;
         }
@@ -1471,6 +1481,11 @@ __global__ __launch_bounds__(BORE_THREADS) void fit_kernel(const FitArgs a) {
 template <int SHAPE>
 __global__ __launch_bounds__(2 * BORE_THREADS) void fit_kernel_w8(const FitArgs a) {
   fit_body<SHAPE, 8>(a, blockIdx.x);
+}
+// The weighted fit (bore_mlp_fit_weighted): the generic flavour with a sample weight per row.  The weights are a
+// kernel argument of their own: FitArgs, and with it every other fit kernel's argument block, stays as it is.
+__global__ __launch_bounds__(BORE_THREADS) void fit_weighted_kernel(const FitArgs a, const float *sw) {
+  fit_body<0, 4, true>(a, blockIdx.x, -1, sw);
 }
 
 // ---------------------------------------------------------------------------
@@ -2168,8 +2183,12 @@ struct EvalArgs {
   float *loss, *acc;
   long long N;
   int o_tile, o_misc, o_layout, total;
+  const float *sw;  // sample weights [n_models][N] (the WEIGHTED instantiation alone reads them)
 };
 
+// WEIGHTED: a.sw [n_models][N] weighs each row's loss term (Keras evaluate(sample_weight=...)); the divisor stays N and
+// the accuracy stays unweighted (Keras applies sample weights to weighted_metrics only).
+template <bool WEIGHTED>
 __global__ __launch_bounds__(BORE_THREADS) void evaluate_kernel(const EvalArgs a) {
   extern __shared__ float smem[];
   const MlpLayout &L = stage_layout(a.L, smem, a.total, a.o_layout);
@@ -2195,7 +2214,8 @@ __global__ __launch_bounds__(BORE_THREADS) void evaluate_kernel(const EvalArgs a
       if (lane < 16 && g * 16 + lane < a.N) {
         const float x = tile[L.aoff[n] + (wv * 16 + lane) * L.lda[n]];
         const float zz = z[g * 16 + lane];
-        lsum += bce_loss(x, zz);
+        if constexpr (WEIGHTED) lsum += bce_loss_weighted(x, zz, a.sw[model * a.N + g * 16 + lane]);
+        else lsum += bce_loss(x, zz);
         const float o = L.act[n] == BORE_ACT_SIGMOID ? sigmoid_stable(x) : x;
         csum += accuracy_hit(o, zz);
       }
@@ -2262,6 +2282,7 @@ struct FitRequest {
   int64_t model_index0, epoch0;
   const bore_adam_cfg *adam;
   float *epoch_loss;
+  const float *sample_weight = nullptr;  // bore_mlp_fit_weighted's: device fp32 [n_models][N]; nullptr: the unweighted fit
 };
 static int fit_bf16_impl(const FitRequest &r, void *stream);
 
@@ -2271,8 +2292,8 @@ static bool stream_forced(const bore_mlp_desc *);
 static int stream_forward_entry(const bore_mlp_desc *, int, const float *, const float *, int64_t, int, float *, void *);
 static int stream_value_and_input_grad(const bore_mlp_desc *, int, const float *, const double *, int64_t, int, int,
                                        float *, double *, void *);
-static int stream_evaluate(const bore_mlp_desc *, int, const float *, const float *, const float *, int64_t, float *,
-                           float *, void *);
+static int stream_evaluate(const bore_mlp_desc *, int, const float *, const float *, const float *, const float *,
+                           int64_t, float *, float *, void *);
 static int stream_fit(const FitRequest &r, void *stream);
 static bool stream_takes(const bore_mlp_desc *desc, int rc) {
   return rc == BORE_E_UNSUPPORTED && desc && desc->compute == BORE_COMPUTE_F32 && !g_batch;
@@ -2313,8 +2334,10 @@ struct FitPlan {
 
 // Capacity checks, LDS carve and kernel flavour of a float32 fit: no pointer of the request is looked at, `batch` is
 // the batch mode it runs in (bore_set_batch; nullptr: none).  bore_mlp_streamed and fit_padded ask it on its own.
+// `weighted` (a request with sample weights): flavour 0 whatever the network -- the one LDS kernel that reads them;
+// its carve is the unweighted generic one (the weights are read from memory), so the capacity answers are too.
 static int fit_plan(const bore_mlp_desc *desc, int n_models, int64_t N, int batch_size, bool perm,
-                    const bore_batch *batch, FitPlan &p) {
+                    const bore_batch *batch, FitPlan &p, bool weighted = false) {
   FitArgs &a = p.a;
   p.fits = false;
   if (batch_size < 1) return fail(BORE_E_INVALID, "fit: batch_size must be positive (got %d)", batch_size);
@@ -2324,13 +2347,13 @@ static int fit_plan(const bore_mlp_desc *desc, int n_models, int64_t N, int batc
   const int tile_rows = batch_size < BORE_BATCH_MAX ? batch_size : BORE_BATCH_MAX;
   // (the parked-row slots of fit_body: the narrow static shapes only -- a wide one has no LDS to spare)
   // (the fit-only static shape: not in batch mode -- the fused iteration kernels have no case for it)
-  const int fl = !desc ? 0 : batch ? bore_kernel_flavour(desc, batch_size == BORE_BATCH_MAX)
-                                   : bore_fit_flavour(desc, batch_size == BORE_BATCH_MAX);
+  const int fl = !desc || weighted ? 0 : batch ? bore_kernel_flavour(desc, batch_size == BORE_BATCH_MAX)
+                                               : bore_fit_flavour(desc, batch_size == BORE_BATCH_MAX);
   const size_t stage_f = fl > 0 && !bore_shape_is_wide(fl) ? BORE_FIT_STAGE_FLOATS_OF(fl) : 0;
   const size_t fixed_extra = BORE_BATCH_MAX + 8 + stage_f + BORE_LAYOUT_FLOATS + 12;
   // 32->128-128-1 in float32 with 64-row batches: theta and the 64-row images do not share the LDS;
   // the weight gradients are formed in four rounds over 16-row images instead (wide_rounds_f32)
-  const bool rounds = desc && desc->compute != BORE_COMPUTE_BF16 && batch_size == BORE_BATCH_MAX && !batch &&
+  const bool rounds = desc && desc->compute != BORE_COMPUTE_BF16 && batch_size == BORE_BATCH_MAX && !batch && !weighted &&
                       bore_shape_fit_in_rounds(bore_kernel_flavour(desc, true));
   int rc = 0;
   if (rounds) {
@@ -2458,7 +2481,8 @@ static bool fit_wants_w8(int n_models, int forced, int cus) { return forced < 0 
 // request's own checks, its fields.  The request's faults are reported before a carve that does not fit -- the plan's
 // message stands when there are none.  Returns 1 when there is nothing to do (epochs == 0).
 static int fit_build(const FitRequest &r, FitPlan &p) {
-  const int planned = fit_plan(r.desc, r.n_models, r.N, r.batch_size, r.perm != nullptr, g_batch, p);
+  const int planned = fit_plan(r.desc, r.n_models, r.N, r.batch_size, r.perm != nullptr, g_batch, p,
+                               r.sample_weight != nullptr);
   if (planned && !p.fits) return planned;
   if (const int rc = fit_check_request(p.a.L, r)) return rc;
   if (g_batch && (r.perm || r.epoch_loss)) return fail(BORE_E_INVALID, "fit: no perm / epoch_loss in batch mode");
@@ -2548,14 +2572,30 @@ extern "C" int bore_mlp_fit(const bore_mlp_desc *desc, int n_models, float *thet
                  stream);
 }
 
+extern "C" int bore_mlp_fit_weighted(const bore_mlp_desc *desc, int n_models, float *theta, float *adam_m,
+                                     float *adam_v, int64_t *adam_t, const float *X, const float *z,
+                                     const float *sample_weight, int64_t N, int epochs, int batch_size,
+                                     const int32_t *perm, uint64_t seed, int64_t model_index0, int64_t epoch0,
+                                     const bore_adam_cfg *adam, float *epoch_loss, void *stream) {
+  return fit_run(FitRequest{desc, n_models, theta, adam_m, adam_v, adam_t, X, z, N, epochs, batch_size, perm, seed,
+                            model_index0, epoch0, adam, epoch_loss, sample_weight},
+                 stream);
+}
+
 static int fit_run(const FitRequest &r, void *stream) {
   const bore_mlp_desc *desc = r.desc;
   const int n_models = r.n_models;
+  // A weighted request (sample_weight): the generic flavour or the streamed one and nothing else -- no bfloat16, no
+  // batch mode, no zero-padded detour, no static or eight-wave kernel (fit_plan).
+  const bool weighted = r.sample_weight != nullptr;
+  if (weighted && desc && desc->compute == BORE_COMPUTE_BF16)
+    return fail(BORE_E_UNSUPPORTED, "fit: weighted fits are float32 only (compute = bfloat16 takes no sample_weight)");
+  if (weighted && g_batch) return fail(BORE_E_UNSUPPORTED, "fit: no sample_weight in batch mode (bore_set_batch)");
   // (BORE_STREAM = 1: in front of everything, the zero-padded detour included)
   if (stream_forced(desc)) return stream_fit(r, stream);
   // (BORE_FIT_PAD = 0: such nets on the generic flavour, as before round 4 -- A/B, tests)
   // (fit_padded leaves a request with a fault of its own, or with nothing to do, to the checks below)
-  if (desc && !g_batch && r.batch_size == BORE_BATCH_MAX && !(getenv("BORE_FIT_PAD") && !atoi(getenv("BORE_FIT_PAD")))) {
+  if (desc && !g_batch && !weighted && r.batch_size == BORE_BATCH_MAX && !(getenv("BORE_FIT_PAD") && !atoi(getenv("BORE_FIT_PAD")))) {
     const int S = bore_pads_to_shape(desc);
     if (S) {
       const int rc = fit_padded(r, S, stream);
@@ -2571,6 +2611,11 @@ static int fit_run(const FitRequest &r, void *stream) {
   // (refused for capacity: the streamed flavour, or its own bound by name)
   if (stream_takes(desc, rc)) return stream_fit(r, stream);
   if (rc) return rc < 0 ? rc : 0;
+  if (weighted)
+    return bore_with_flavour(FlavourList<0>{}, p.flavour, [&](auto) {
+      return launch_lds(fit_weighted_kernel, dim3(n_models), dim3(BORE_THREADS), p.lds_floats * 4, stream, p.a,
+                        r.sample_weight);
+    });
   const int forced = getenv("BORE_FIT_W8") ? atoi(getenv("BORE_FIT_W8")) : -1;
   if (p.w8 && fit_wants_w8(n_models, forced, device_cus()))
     return bore_with_flavour(FitW8Flavours{}, p.flavour, [&](auto S) {
@@ -2713,13 +2758,13 @@ extern "C" int bore_mlp_value_and_input_grad(const bore_mlp_desc *desc, int n_mo
   return row_launch(true, n_models, a, stream);
 }
 
-extern "C" int bore_mlp_evaluate(const bore_mlp_desc *desc, int n_models, const float *theta,
-                                 const float *X, const float *z, int64_t N, float *loss,
-                                 float *acc, void *stream) {
+// bore_mlp_evaluate and bore_mlp_evaluate_weighted (sample_weight != nullptr): the same checks, carve and route.
+static int evaluate_run(const bore_mlp_desc *desc, int n_models, const float *theta, const float *X, const float *z,
+                        const float *sample_weight, int64_t N, float *loss, float *acc, void *stream) {
   EvalArgs a;
-  if (stream_forced(desc)) return stream_evaluate(desc, n_models, theta, X, z, N, loss, acc, stream);
+  if (stream_forced(desc)) return stream_evaluate(desc, n_models, theta, X, z, sample_weight, N, loss, acc, stream);
   int rc = check_common(desc, n_models, 0, BORE_BATCH_MAX, true, 8 + BORE_LAYOUT_FLOATS + 4, &a.L);
-  if (stream_takes(desc, rc)) return stream_evaluate(desc, n_models, theta, X, z, N, loss, acc, stream);
+  if (stream_takes(desc, rc)) return stream_evaluate(desc, n_models, theta, X, z, sample_weight, N, loss, acc, stream);
   if (rc) return rc;
   if (a.L.w[a.L.n_layers] != 1)
     return fail(BORE_E_INVALID, "evaluate: the last Dense layer must have 1 unit");
@@ -2732,7 +2777,21 @@ extern "C" int bore_mlp_evaluate(const bore_mlp_desc *desc, int n_models, const 
   a.total = (int)off;
   off = (off + 3) & ~(size_t)3;
   a.o_layout = (int)off; off += BORE_LAYOUT_FLOATS;
-  return launch_lds(evaluate_kernel, dim3(n_models), dim3(BORE_THREADS), off * 4, stream, a);
+  a.sw = sample_weight;
+  if (sample_weight) return launch_lds(evaluate_kernel<true>, dim3(n_models), dim3(BORE_THREADS), off * 4, stream, a);
+  return launch_lds(evaluate_kernel<false>, dim3(n_models), dim3(BORE_THREADS), off * 4, stream, a);
+}
+
+extern "C" int bore_mlp_evaluate(const bore_mlp_desc *desc, int n_models, const float *theta,
+                                 const float *X, const float *z, int64_t N, float *loss,
+                                 float *acc, void *stream) {
+  return evaluate_run(desc, n_models, theta, X, z, nullptr, N, loss, acc, stream);
+}
+
+extern "C" int bore_mlp_evaluate_weighted(const bore_mlp_desc *desc, int n_models, const float *theta,
+                                          const float *X, const float *z, const float *sample_weight, int64_t N,
+                                          float *loss, float *acc, void *stream) {
+  return evaluate_run(desc, n_models, theta, X, z, sample_weight, N, loss, acc, stream);
 }
 
 extern "C" int bore_shuffle_perm(uint64_t seed, int64_t model_index0, int n_models,

@@ -595,8 +595,11 @@ struct StreamEvalArgs {
   long long N;
   float *ws;
   long long ws_stride;
+  const float *sw;  // sample weights [n_models][N] (the WEIGHTED instantiation alone reads them)
 };
 
+// WEIGHTED: a.sw [n_models][N] weighs each row's loss term; the divisor stays N, the accuracy stays unweighted.
+template <bool WEIGHTED>
 __global__ __launch_bounds__(BORE_THREADS) void stream_evaluate_kernel(const StreamEvalArgs a) {
   __shared__ StreamLds S;
   const MlpLayout &L = stream_begin(S, a.L);
@@ -617,7 +620,8 @@ __global__ __launch_bounds__(BORE_THREADS) void stream_evaluate_kernel(const Str
     if (tid < nr) {
       const float x = An[tid];
       const float zz = z[row0 + tid];
-      lsum += bce_loss(x, zz);
+      if constexpr (WEIGHTED) lsum += bce_loss_weighted(x, zz, a.sw[model * a.N + row0 + tid]);
+      else lsum += bce_loss(x, zz);
       const float o = L.act[n] == BORE_ACT_SIGMOID ? sigmoid_stable(x) : x;
       csum += accuracy_hit(o, zz);
     }
@@ -647,8 +651,12 @@ struct StreamFitArgs {
   float *ws;
   long long ws_stride;  // floats per model: the tile's A / D, then (B > 64) the gradient sums [P]
   long long o_g;
+  const float *sw;  // sample weights [n_models][N] (the WEIGHTED instantiation alone reads them)
 };
 
+// WEIGHTED: a.sw [n_models][N], a sample weight per row: the row's loss term and d loss / d logit are scaled by it, the
+// divisor of the batch mean stays the row count (the weighted fit of bore_hip.hip's generic flavour, streamed).
+template <bool WEIGHTED>
 __global__ __launch_bounds__(BORE_THREADS) void stream_fit_kernel(const StreamFitArgs a) {
   __shared__ StreamLds S;
   const MlpLayout &L = stream_begin(S, a.L);
@@ -658,6 +666,7 @@ __global__ __launch_bounds__(BORE_THREADS) void stream_fit_kernel(const StreamFi
   float *th = a.theta + model * P, *mg = a.am + model * P, *vg = a.av + model * P;
   const float *Xg = a.X + model * (long long)N * D;
   const float *zg = a.z + model * (long long)N;
+  [[maybe_unused]] const float *swg = WEIGHTED ? a.sw + model * (long long)N : nullptr;
   float *ws = a.ws + model * a.ws_stride;
   float *gsum = ws + a.o_g;  // weight-gradient sums carried between the sub-tiles of a batch of more than 64 rows
   float *A0 = ws, *An = ws + SROWS * S.pre[n];
@@ -690,12 +699,16 @@ __global__ __launch_bounds__(BORE_THREADS) void stream_fit_kernel(const StreamFi
           A0[i] = Xg[(long long)perm[r0 + r] * D + d];
         }
         if (tid < nr) S.zt[tid] = zg[perm[r0 + tid]];
+        [[maybe_unused]] float wrow = 0.f;  // (WEIGHTED) this work-item's row's weight: requested here, used at the loss
+        if constexpr (WEIGHTED)
+          if (tid < nr) wrow = swg[perm[r0 + tid]];
         __syncthreads();
         stream_forward<true>(S, L, th, ws, nr, true);
         if (tid < nr) {  // loss and d loss / d logit
           const float x = An[tid];
           const float zz = S.zt[tid];
-          Dn[tid] = fit_bce(x, zz, true, eloss) * inv_nb;
+          if constexpr (WEIGHTED) Dn[tid] = (fit_bce_weighted(x, zz, wrow, true, eloss) * inv_nb) * wrow;
+          else Dn[tid] = fit_bce(x, zz, true, eloss) * inv_nb;
         }
         __syncthreads();
         // ---- per layer, descending: D_{l-1} from the OLD W_l, then dW_l = A_{l-1}^T D_l and its Adam update ----
@@ -838,7 +851,7 @@ static int stream_value_and_input_grad(const bore_mlp_desc *desc, int n_models, 
 }
 
 static int stream_evaluate(const bore_mlp_desc *desc, int n_models, const float *theta, const float *X, const float *z,
-                           int64_t N, float *loss, float *acc, void *stream) {
+                           const float *sample_weight, int64_t N, float *loss, float *acc, void *stream) {
   StreamEvalArgs a;
   if (const int rc = stream_bounds(desc, &a.L)) return rc;
   if (n_models < 1) return fail(BORE_E_INVALID, "n_models must be >= 1 (got %d)", n_models);
@@ -849,7 +862,9 @@ static int stream_evaluate(const bore_mlp_desc *desc, int n_models, const float 
   a.ws_stride = (long long)stream_tile_floats(a.L);
   hipStream_t st = (hipStream_t)stream;
   HIP_TRY(hipMallocAsync((void **)&a.ws, (size_t)n_models * a.ws_stride * sizeof(float), st));
-  hipLaunchKernelGGL(stream_evaluate_kernel, dim3(n_models), dim3(BORE_THREADS), 0, st, a);
+  a.sw = sample_weight;
+  if (sample_weight) hipLaunchKernelGGL(stream_evaluate_kernel<true>, dim3(n_models), dim3(BORE_THREADS), 0, st, a);
+  else hipLaunchKernelGGL(stream_evaluate_kernel<false>, dim3(n_models), dim3(BORE_THREADS), 0, st, a);
   const hipError_t e = hipGetLastError();
   (void)hipFreeAsync(a.ws, st);
   if (e != hipSuccess) return fail(BORE_E_HIP, "streamed evaluate kernel: %s", hipGetErrorString(e));
@@ -893,7 +908,9 @@ static int stream_fit(const FitRequest &r, void *stream) {
     a.perm = drawn;
   }
   if (rc == 0) {
-    hipLaunchKernelGGL(stream_fit_kernel, dim3(n_models), dim3(BORE_THREADS), 0, st, a);
+    a.sw = r.sample_weight;
+    if (r.sample_weight) hipLaunchKernelGGL(stream_fit_kernel<true>, dim3(n_models), dim3(BORE_THREADS), 0, st, a);
+    else hipLaunchKernelGGL(stream_fit_kernel<false>, dim3(n_models), dim3(BORE_THREADS), 0, st, a);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) rc = fail(BORE_E_HIP, "streamed fit kernel: %s", hipGetErrorString(e));
   }

@@ -97,6 +97,8 @@ __device__ __forceinline__ void objective_transform(int transform, float u, floa
 __device__ __forceinline__ float bce_loss(float x, float z) {
   return fmaxf(x, 0.f) - x * z + log1pf(expf(-fabsf(x)));
 }
+// The same under a sample weight w (Keras sample_weight / class_weight): the row's term of sum_i w_i loss_i.
+__device__ __forceinline__ float bce_loss_weighted(float x, float z, float w) { return w * bce_loss(x, z); }
 // 1 where the output o (a probability, or whatever a head without a sigmoid gives) and the label z lie
 // on the same side of 0.5 (Keras binary_accuracy), else 0.
 __device__ __forceinline__ float accuracy_hit(float o, float z) { return ((o > 0.5f) == (z > 0.5f)) ? 1.f : 0.f; }
@@ -109,6 +111,15 @@ __device__ __forceinline__ float fit_bce(float x, float z, bool want_loss, float
   const float sig = x >= 0.f ? rden : ex * rden;
   if (want_loss) loss += fmaxf(x, 0.f) - x * z + log1pf(ex);
   return sig - z;
+}
+// The weighted fit (sample weight w of the row): the same sigmoid(x) - z, and w times the row's loss term added to
+// `loss`.  The caller forms (fit_bce_weighted(...) * inv_nb) * w, in that order: the divisor stays the ROW COUNT
+// (Keras' SUM_OVER_BATCH_SIZE), and with w == 1 every intermediate is the unweighted kernel's, bit for bit.
+__device__ __forceinline__ float fit_bce_weighted(float x, float z, float w, bool want_loss, float &loss) {
+  float l = 0.f;
+  const float d = fit_bce(x, z, want_loss, l);
+  if (want_loss) loss += w * l;
+  return d;
 }
 
 // Adam update of one parameter (ResourceApplyAdam, non-nesterov); returns the new weight.

@@ -52,6 +52,42 @@ def classification_labels(y, gamma):
     return np.less(y, np.quantile(y, q=gamma))
 
 
+def _host_array(a):
+    """numpy view of an array-like or a torch tensor (downloaded)."""
+    return a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+
+
+def resolve_sample_weight(n_rows, y=None, sample_weight=None, class_weight=None):
+    """Keras ``fit(sample_weight=, class_weight=)`` as ONE float32 vector of ``n_rows`` row weights, or None when
+    neither is given (the unweighted fit).  Pure host code.
+
+    ``sample_weight``: shape (N,) or (N, 1).  ``class_weight``: ``{0: a, 1: b}`` -- the row's weight is multiplied by
+    ``b`` where the label is 1 and by ``a`` otherwise (``y``: the labels, needed for it alone); with both given the
+    two multiply (in float64, rounded to float32 once).  Anything else is a ``ValueError``."""
+    if sample_weight is None and class_weight is None:
+        return None
+    n_rows = int(n_rows)
+    w = np.ones(n_rows, dtype=np.float64)
+    if sample_weight is not None:
+        sw = _host_array(sample_weight)
+        if sw.shape not in ((n_rows,), (n_rows, 1)):
+            raise ValueError(f"sample_weight: expected shape ({n_rows},) or ({n_rows}, 1), got {sw.shape}")
+        if sw.dtype.kind not in "fiub":
+            raise ValueError(f"sample_weight: expected numbers, got dtype {sw.dtype}")
+        w = w * sw.reshape(n_rows).astype(np.float64)
+    if class_weight is not None:
+        if not isinstance(class_weight, dict) or set(class_weight) != {0, 1}:
+            raise ValueError("class_weight: expected a dict with exactly the keys 0 and 1 (a binary classifier), got "
+                             f"{class_weight!r}")
+        if y is None:
+            raise ValueError("class_weight needs the labels")
+        z = _host_array(y).reshape(-1)
+        if z.shape != (n_rows,):
+            raise ValueError(f"class_weight: {z.shape[0]} labels for {n_rows} rows")
+        w = w * np.where(z.astype(np.float64) == 1.0,float(class_weight[1]), float(class_weight[0]))
+    return np.ascontiguousarray(w, dtype=np.float32)
+
+
 class MultiFidelityRecord:
     """Observations of a Hyperband run, keyed by configuration and budget (behaviour of
     bore/data.py:51-261).  A rung is a budget; rungs are numbered by increasing budget.  Labels at a rung

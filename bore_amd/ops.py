@@ -92,9 +92,13 @@ def mlp_value_and_input_grad(desc, theta, X, transform="identity", negate=True, 
 
 
 def mlp_fit(desc, theta, m, v, t, X, z, epochs, batch_size, perm=None, seed=0, model_index0=0,
-            epoch0=0, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-7, want_loss=True):
+            epoch0=0, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-7, want_loss=True, sample_weight=None):
     """In-place Keras-form fit of L models.  Returns epoch_loss [L,epochs] f32 (or None).
-    (desc.compute = bfloat16: mixed precision, include/bore_hip.h enum bore_compute.)"""
+    (desc.compute = bfloat16: mixed precision, include/bore_hip.h enum bore_compute.)
+
+    ``sample_weight`` [L,N] f32: a weight per row (``bore_mlp_fit_weighted``: the batch loss is
+    ``sum_i w_i loss_i / rows``); float32 networks on the generic or the streamed flavour, ``UnsupportedError`` with
+    compute = bfloat16.  None: the unweighted fit."""
     L, P = theta.shape
     D = desc.input_dim
     _chk(theta, torch.float32, (L, param_count(desc)), "theta")
@@ -106,6 +110,8 @@ def mlp_fit(desc, theta, m, v, t, X, z, epochs, batch_size, perm=None, seed=0, m
     N = X.shape[1]
     _chk(X, torch.float32, (L, N, D), "X")
     _chk(z, torch.float32, (L, N), "z")
+    if sample_weight is not None:
+        _chk(sample_weight, torch.float32, (L, N), "sample_weight")
     epochs = int(epochs)
     if perm is not None:
         _chk(perm, torch.int32, (L, epochs, N), "perm")
@@ -114,15 +120,19 @@ def mlp_fit(desc, theta, m, v, t, X, z, epochs, batch_size, perm=None, seed=0, m
             raise ValueError("perm: entries must lie in [0, N)")
     loss = torch.empty((L, epochs), dtype=torch.float32, device=theta.device) if want_loss else None
     cfg = _lib.AdamCfg(lr, beta1, beta2, eps)
-    _lib.check(_lib.lib().bore_mlp_fit(
-        C.byref(desc), L, _lib.ptr(theta), _lib.ptr(m), _lib.ptr(v), _lib.ptr(t), _lib.ptr(X),
-        _lib.ptr(z), N, epochs, int(batch_size), _lib.ptr(perm), C.c_uint64(seed & (2**64 - 1)),
-        int(model_index0), int(epoch0), C.byref(cfg), _lib.ptr(loss), _lib.stream_ptr()))
+    tail = (N, epochs, int(batch_size), _lib.ptr(perm), C.c_uint64(seed & (2**64 - 1)),
+            int(model_index0), int(epoch0), C.byref(cfg), _lib.ptr(loss), _lib.stream_ptr())
+    head = (C.byref(desc), L, _lib.ptr(theta), _lib.ptr(m), _lib.ptr(v), _lib.ptr(t), _lib.ptr(X), _lib.ptr(z))
+    if sample_weight is None:
+        _lib.check(_lib.lib().bore_mlp_fit(*head, *tail))
+    else:
+        _lib.check(_lib.lib().bore_mlp_fit_weighted(*head, _lib.ptr(sample_weight), *tail))
     return loss
 
 
-def mlp_evaluate(desc, theta, X, z):
-    """-> (loss [L] f32, accuracy [L] f32)."""
+def mlp_evaluate(desc, theta, X, z, sample_weight=None):
+    """-> (loss [L] f32, accuracy [L] f32).  ``sample_weight`` [L,N] f32: loss = sum_i w_i loss_i / N (+ l2); the
+    accuracy stays unweighted (``bore_mlp_evaluate_weighted``)."""
     L, P = theta.shape
     D = desc.input_dim
     _chk(theta, torch.float32, (L, param_count(desc)), "theta")
@@ -131,9 +141,15 @@ def mlp_evaluate(desc, theta, X, z):
     _chk(z, torch.float32, (L, N), "z")
     loss = torch.empty(L, dtype=torch.float32, device=theta.device)
     acc = torch.empty(L, dtype=torch.float32, device=theta.device)
-    _lib.check(_lib.lib().bore_mlp_evaluate(C.byref(desc), L, _lib.ptr(theta), _lib.ptr(X),
-                                            _lib.ptr(z), N, _lib.ptr(loss), _lib.ptr(acc),
-                                            _lib.stream_ptr()))
+    if sample_weight is None:
+        _lib.check(_lib.lib().bore_mlp_evaluate(C.byref(desc), L, _lib.ptr(theta), _lib.ptr(X),
+                                                _lib.ptr(z), N, _lib.ptr(loss), _lib.ptr(acc),
+                                                _lib.stream_ptr()))
+    else:
+        _chk(sample_weight, torch.float32, (L, N), "sample_weight")
+        _lib.check(_lib.lib().bore_mlp_evaluate_weighted(C.byref(desc), L, _lib.ptr(theta), _lib.ptr(X), _lib.ptr(z),
+                                                         _lib.ptr(sample_weight), N, _lib.ptr(loss), _lib.ptr(acc),
+                                                         _lib.stream_ptr()))
     return loss, acc
 
 

@@ -166,6 +166,27 @@ int bore_mlp_fit(const bore_mlp_desc *desc, int n_models, float *theta,
                  void *stream);
 
 /*
+ * The same fit under Keras' sample_weight / class_weight: a step over a batch of nb rows minimises
+ * (1/nb) sum_i w_i loss_i + the l2 penalties -- the divisor is the ROW COUNT (reduction
+ * SUM_OVER_BATCH_SIZE), not sum w -- so d loss / d logit_i = w_i (sigmoid(x_i) - z_i) / nb, and the logged
+ * epoch loss is sum_i w_i loss_i / N plus the penalty term as above.
+ *   sample_weight  device fp32 [n_models][N], one weight per row (a class weight is folded in by the caller:
+ *                  w_i times b where z_i = 1, times a otherwise); NULL: exactly the call above
+ * Unit weights give the bits of the unweighted fit.  A weighted fit runs on the kernels whose layout is a
+ * run-time argument and on no other: the generic flavour for every network that fits one workgroup's LDS -- also
+ * one with a compile-time layout above, which the generic flavour fits in 2.4 - 2.6x the static kernel's time at
+ * the 32-32-1 widths and 3.5x at 16->32-32-32-1, to the same bits -- and the streamed flavour exactly when the
+ * unweighted call would take it.  BORE_E_UNSUPPORTED with compute = bfloat16 ("weighted fits are float32 only"), in batch mode, and for a network neither flavour
+ * takes (the unweighted call's message).
+ */
+int bore_mlp_fit_weighted(const bore_mlp_desc *desc, int n_models, float *theta,
+                          float *adam_m, float *adam_v, int64_t *adam_t, const float *X,
+                          const float *z, const float *sample_weight, int64_t N, int epochs,
+                          int batch_size, const int32_t *perm, uint64_t seed,
+                          int64_t model_index0, int64_t epoch0, const bore_adam_cfg *adam,
+                          float *epoch_loss, void *stream);
+
+/*
  * Keras evaluate(X, z): mean BCE(+l2) and binary accuracy (threshold 0.5 on the
  * model output) over all N rows (bore/plugins/hpbandster/base.py:186).
  *   loss, acc  device fp32 [n_models]
@@ -173,6 +194,16 @@ int bore_mlp_fit(const bore_mlp_desc *desc, int n_models, float *theta,
 int bore_mlp_evaluate(const bore_mlp_desc *desc, int n_models, const float *theta,
                       const float *X, const float *z, int64_t N, float *loss,
                       float *acc, void *stream);
+
+/*
+ * Keras evaluate(X, z, sample_weight=w): loss = sum_i w_i BCE_i / N (+l2); the accuracy stays UNWEIGHTED
+ * (Keras applies sample weights to weighted_metrics only).
+ *   sample_weight  device fp32 [n_models][N]; NULL: exactly the call above
+ * Same route as the call above (generic or streamed kernel); it always reads the float32 weights.
+ */
+int bore_mlp_evaluate_weighted(const bore_mlp_desc *desc, int n_models, const float *theta,
+                               const float *X, const float *z, const float *sample_weight,
+                               int64_t N, float *loss, float *acc, void *stream);
 
 /*
  * Label step of the BO loop: tau = quantile(y, gamma) with numpy's default linear
