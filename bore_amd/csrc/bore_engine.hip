@@ -374,6 +374,10 @@ bore_batch async_batch(const bore_engine *e, const int32_t *ids, const int32_t *
 // resident, or -- more loops than resident workgroups -- the work queue.  bore_engine_cfg::work_queue = 0 / 1 forces the
 // launch-per-batch schedule of round 3 / the queue (tests, A/B).  Called when the engine is created and whenever
 // the records have grown (a longer data set in LDS may cost a loop per CU).
+// Where the chain's three batch-mode plans take the request but the fused kernel does not (iteration_plan: a batch
+// size, or records grown to a length, at which the fit leaves the static kernel), the engine takes the launch chain
+// from here on: `fused` and `wait_ticks` are cleared.  A loop's state lives in global memory between iterations, and
+// no workgroup is resident between two runs, so the trajectories do not change.
 static int async_decide_schedule(bore_engine *e) {
   Async &A = *e->as;
   const bore_engine_cfg &c = e->cfg;
@@ -389,8 +393,20 @@ static int async_decide_schedule(bore_engine *e) {
   IterPlan plan;
   int rc = iteration_plan(A.eng, w, L, &probe, &plan);
   bore_set_batch(nullptr);
-  if (rc || (rc = iteration_loops_per_cu(plan.shape, plan.lds_bytes, &per_cu))) return rc;
-  if (per_cu < 1) return fail(BORE_E_UNSUPPORTED, "engine: the fused kernel does not fit a compute unit with records of %lld rows", (long long)A.cap);
+  if (!rc && !(rc = iteration_loops_per_cu(plan.shape, plan.lds_bytes, &per_cu)) && per_cu < 1) {
+    plan.shape = 0;  // (planned, but a loop's LDS is more than a CU has: the chain's kernels each take less)
+    rc = BORE_E_UNSUPPORTED;
+  }
+  if (rc == BORE_E_UNSUPPORTED && plan.shape == 0) {
+    g_bore_err[0] = 0;
+    A.fused = false;
+    A.wait_ticks = 0;
+    A.per_cu = 0;
+    if (getenv("BORE_ASYNC_DEBUG"))
+      fprintf(stderr, "[bore] engine: %d loops, records of %lld rows: no fused kernel -> the launch chain\n", L, (long long)A.cap);
+    return 0;
+  }
+  if (rc) return rc;
   A.per_cu = per_cu;
   const int forced = c.work_queue;
   const int resident_cap = per_cu * device_cus();
@@ -478,7 +494,35 @@ int async_create(bore_engine *e, const double *X0, const double *y0) {
   A.scratch_ids.reserve(L); A.cb_x.resize(L * D); A.cb_y.resize(L);
   A.launched_at.assign(L, 0.0);
   A.done_ids.assign(L, 0);
+  // One staging block per worker and side -- IterArgs | x_new [L][D] | y_new [L] | ids [L] | its [L] |
+  // targets [L] -- so that a launch is preceded by one upload (each small copy is its own ~30 us
+  // blit packet)
+  auto make_worker = [&](Worker &w) -> int {
+    int rc;
+    HIP_TRY(hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
+    HIP_TRY(hipEventCreateWithFlags(&w.done, hipEventDisableTiming));
+    for (hipEvent_t &ev : w.ev) HIP_TRY(hipEventCreate(&ev));
+    w.stage_bytes = ((sizeof(IterArgs) + 15) & ~(size_t)15) + L * (D + 1) * 8 + 3 * L * 4;
+    char *hb = nullptr, *db = nullptr;
+    if ((rc = pin_alloc(&hb, w.stage_bytes)) || (rc = dev_alloc(&db, w.stage_bytes))) return rc;
+    const size_t o_dbl = (sizeof(IterArgs) + 15) & ~(size_t)15, o_int = o_dbl + L * (D + 1) * 8;
+    w.h_args = reinterpret_cast<IterArgs *>(hb); w.d_args = reinterpret_cast<IterArgs *>(db);
+    w.h_dbl = reinterpret_cast<double *>(hb + o_dbl); w.d_dbl = reinterpret_cast<double *>(db + o_dbl);
+    w.h_int = reinterpret_cast<int32_t *>(hb + o_int); w.d_int = reinterpret_cast<int32_t *>(db + o_int);
+    if ((rc = dev_alloc(&w.x0, L * R * D)) || (rc = dev_alloc(&w.x, L * R * D)) ||
+        (rc = dev_alloc(&w.jac, L * R * D)) || (rc = dev_alloc(&w.fun, L * R)) ||
+        (rc = dev_alloc(&w.idx, L * R)) || (rc = dev_alloc(&w.info, L * R * 5)))
+      return rc;
+    return 0;
+  };
+  // The first worker, and with it the plan of a fused launch: the network alone does not say whether the fused kernel
+  // runs (a batch size other than the static fit's sends the fit elsewhere) -- the schedule is decided here, before
+  // the workers are sized, and a request that only the chain takes runs the chain.  What neither takes is refused
+  // now, before any launch.
+  A.workers.resize(1);
+  if ((rc = make_worker(A.workers[0]))) return rc;
   A.fused = iteration_shape(&e->desc) != 0;
+  if ((rc = async_decide_schedule(e))) return rc;
   // Residency: a loop's workgroup stays on its CU between iterations and waits this long for the
   // objective value before it gives its slot up (bore_engine_cfg::resident_wait_us; 0 = one iteration per
   // launch).  Dropped by the launcher when the device cannot hold all loops at once.
@@ -492,25 +536,8 @@ int async_create(bore_engine *e, const double *X0, const double *y0) {
   if (A.fused && n_workers > queues - 2) n_workers = queues - 2 > 2 ? queues - 2 : 2;
   if (e->cfg.worker_streams > 0) n_workers = e->cfg.worker_streams;
   A.workers.resize(n_workers > 0 ? n_workers : 1);
-  for (Worker &w : A.workers) {
-    HIP_TRY(hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreateWithFlags(&w.done, hipEventDisableTiming));
-    for (hipEvent_t &ev : w.ev) HIP_TRY(hipEventCreate(&ev));
-    // ONE staging block per side -- IterArgs | x_new [L][D] | y_new [L] | ids [L] | its [L] |
-    // targets [L] -- so that a launch is preceded by one upload (each small copy is its own ~30 us
-    // blit packet)
-    w.stage_bytes = ((sizeof(IterArgs) + 15) & ~(size_t)15) + L * (D + 1) * 8 + 3 * L * 4;
-    char *hb = nullptr, *db = nullptr;
-    if ((rc = pin_alloc(&hb, w.stage_bytes)) || (rc = dev_alloc(&db, w.stage_bytes))) return rc;
-    const size_t o_dbl = (sizeof(IterArgs) + 15) & ~(size_t)15, o_int = o_dbl + L * (D + 1) * 8;
-    w.h_args = reinterpret_cast<IterArgs *>(hb); w.d_args = reinterpret_cast<IterArgs *>(db);
-    w.h_dbl = reinterpret_cast<double *>(hb + o_dbl); w.d_dbl = reinterpret_cast<double *>(db + o_dbl);
-    w.h_int = reinterpret_cast<int32_t *>(hb + o_int); w.d_int = reinterpret_cast<int32_t *>(db + o_int);
-    if ((rc = dev_alloc(&w.x0, L * R * D)) || (rc = dev_alloc(&w.x, L * R * D)) ||
-        (rc = dev_alloc(&w.jac, L * R * D)) || (rc = dev_alloc(&w.fun, L * R)) ||
-        (rc = dev_alloc(&w.idx, L * R)) || (rc = dev_alloc(&w.info, L * R * 5)))
-      return rc;
-  }
+  for (size_t k = 1; k < A.workers.size(); ++k)
+    if ((rc = make_worker(A.workers[k]))) return rc;
   // Do the worker streams really run side by side?  ROCm multiplexes streams onto
   // GPU_MAX_HW_QUEUES hardware queues, fixed when the runtime initialised (default 4): a caller
   // that touched the GPU before that variable was set gets fewer queues than streams, and streams
@@ -552,7 +579,7 @@ int async_create(bore_engine *e, const double *X0, const double *y0) {
                 1e3 * one, A.workers.size(), 1e3 * dt, conc, queues, A.workers.size());
     }
   }
-  return async_decide_schedule(e);
+  return 0;
 }
 
 void async_destroy(bore_engine *e) {

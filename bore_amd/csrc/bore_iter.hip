@@ -489,8 +489,11 @@ struct IterPlan {
 // What a fused launch of `n_slots` loops of the batch currently set (bore_set_batch) on worker w needs: fills the
 // arguments *h, says which static shape runs the model and how much LDS a loop takes, and raises the fused kernels'
 // LDS limits to that.  Asked on its own by the engine's choice of schedule; both launches below start from it.
-// BORE_E_UNSUPPORTED when the model is neither static shape 1 nor 5 at 16 inputs: the caller keeps the launch chain.
+// BORE_E_UNSUPPORTED with plan->shape == 0 when the three batch-mode plans take the request, but not as one workgroup
+// of static shape 1, or 5 at 16 inputs (another model; a batch size or a record length at which the fit leaves the
+// static kernel): the caller keeps the launch chain.  Any other refusal (plan->shape < 0) is one of the chain's too.
 static int iteration_plan(const IterEngine &E, const Worker &w, int n_slots, IterArgs *h, IterPlan *plan) {
+  plan->shape = -1;
   if (!g_batch) return fail(BORE_E_INVALID, "iteration_launch: no batch set");
   const int64_t cap = g_batch->cap;
   FitPlan fit;
@@ -513,8 +516,10 @@ static int iteration_plan(const IterEngine &E, const Worker &w, int n_slots, Ite
   h->s = screen.a; h->b = restarts.a;
   const size_t ls = screen.lds_floats, lb = restarts.lds_floats;
   const int shape = iteration_shape(E.desc);
-  if (!shape || sf != shape || screen.flavour != shape || restarts.flavour != shape || restarts.blocks != 1)
+  if (!shape || sf != shape || screen.flavour != shape || restarts.flavour != shape || restarts.blocks != 1) {
+    plan->shape = 0;
     return fail(BORE_E_UNSUPPORTED, "iteration_launch: static shape 1, or 5 at 16 inputs, one workgroup per loop");
+  }
   h->X_seen = E.X_seen; h->y_seen = E.y_seen; h->X32 = E.X32; h->z = E.z;
   h->x_new = w.d_dbl; h->y_new = w.d_dbl + (size_t)E.n_loops * E.desc->input_dim;
   h->stamps = reinterpret_cast<long long *>(g_batch->stamps);

@@ -59,6 +59,20 @@ LBFGSB_DEFAULTS = dict(maxcor=10, ftol=2.2204460492503131e-09, gtol=1e-5, maxfun
                        maxiter=15000, maxls=20)
 
 
+def box(low, high, D):
+    """The search box as two float64 arrays of length D (default: the unit box).  Finite, low <= high (an equal pair
+    fixes that coordinate); anything else is a ValueError, raised before any device call."""
+    lo = np.zeros(D) if low is None else np.array(low, dtype=np.float64)
+    hi = np.ones(D) if high is None else np.array(high, dtype=np.float64)
+    if lo.shape != (D,) or hi.shape != (D,):
+        raise ValueError(f"low and high must have length input_dim = {D} (got shapes {lo.shape} and {hi.shape})")
+    if not (np.isfinite(lo).all() and np.isfinite(hi).all()):
+        raise ValueError("low and high must be finite")
+    if not (lo <= hi).all():
+        raise ValueError("low <= high is needed in every coordinate")
+    return lo, hi
+
+
 def lbfgsb_opts(options):
     o = dict(LBFGSB_DEFAULTS)
     unknown = set(options) - set(o)
@@ -87,8 +101,11 @@ class NativeEngine:
                  transform="identity", gamma=0.25, epochs=200, batch_size=64, num_starts=3,
                  num_samples=1024, n_init=10, objective=branin01, options=None, device=None,
                  seed=0, groups=4, deduplicate=False, async_loops=False, resident_wait_us=None,
-                 worker_streams=None, work_queue=None, compute="float32"):
-        """compute: "float32", or "bfloat16" for the two wide shapes on the bf16 matrix cores (16->64-64-64-1,
+                 worker_streams=None, work_queue=None, compute="float32", low=None, high=None):
+        """low, high: the search box, arrays of length input_dim (default: the unit box; ``low[d] == high[d]`` fixes a
+        coordinate).  The initial design, the candidates, the restarts' bounds and the fallback draw all take it.
+
+        compute: "float32", or "bfloat16" for the two wide shapes on the bf16 matrix cores (16->64-64-64-1,
         32->128-128-1; batch_size 64).  The lock-step schedule runs every network the model API runs: a float32
         network too large for one workgroup's LDS screens and restarts on the streamed kernels (``ops.mlp_streamed``).
         The asynchronous schedule launches in batch mode, which the bfloat16 fit and the streamed kernels refuse: such
@@ -100,6 +117,7 @@ class NativeEngine:
         ABI 12 -- environment variables until round 5): ``resident_wait_us`` how long a loop's workgroup waits on its
         CU for the objective value before it parks (0: one launch per loop-iteration), ``worker_streams``,
         ``work_queue`` False / True: never / always the persistent work-queue launch (default: by size)."""
+        self.low, self.high = box(low, high, int(input_dim))        # (before any device call)
         self.device = device or _lib.require_gpu()
         self.loop_ids = np.asarray(loop_ids, dtype=np.int64)
         self.L = L = len(self.loop_ids)
@@ -122,7 +140,6 @@ class NativeEngine:
             assert D == 2, "branin01 is two-dimensional"
             native, objective = "bore_objective_branin01", branin01
         self.objective = objective
-        self.low, self.high = np.zeros(D), np.ones(D)
         rss, th, X0, y0 = initial_state(self.loop_ids, D, self.units, self.P, n_init, objective,
                                         self.low, self.high)
         mt = np.empty((L, 625), dtype=np.uint32)
@@ -338,8 +355,9 @@ class ReplicaEngine:
                  transform="identity", gamma=0.25, epochs=200, batch_size=64, num_starts=3,
                  num_samples=1024, n_init=10, objective=branin01, max_points=None,
                  options=None, device=None, mode="device", seed=0, groups=1, select="device",
-                 deduplicate=False, compute="float32"):
-        """compute: as ``NativeEngine``'s ("bfloat16": the two wide shapes, batch_size 64).
+                 deduplicate=False, compute="float32", low=None, high=None):
+        """compute, low, high: as ``NativeEngine``'s ("bfloat16": the two wide shapes, batch_size 64; the box:
+        arrays of length input_dim, default the unit box).
 
         mode "device": label, fit, candidate draw, screening and all L-BFGS-B restarts run
         as five launches per BO iteration with ONE host sync (candidates from the device
@@ -364,6 +382,7 @@ class ReplicaEngine:
         assert select in ("device", "host")
         self.select, self.deduplicate = select, bool(deduplicate)
         self.mode, self.seed = mode, int(seed)
+        self.low, self.high = box(low, high, int(input_dim))        # (before any device call)
         self.device = device or _lib.require_gpu()
         self.loop_ids = np.asarray(loop_ids, dtype=np.int64)
         self.L = L = len(self.loop_ids)
@@ -388,7 +407,6 @@ class ReplicaEngine:
         self.num_starts, self.num_samples = int(num_starts), int(num_samples)
         self.objective = objective
         self.options = dict(options or dict(maxiter=1000, ftol=1e-9))
-        self.low, self.high = np.zeros(D), np.ones(D)
         self.rs, th, X0, y0 = initial_state(self.loop_ids, D, self.units, self.P, n_init,
                                             self.objective, self.low, self.high)
         self.theta = torch.from_numpy(th).to(self.device)

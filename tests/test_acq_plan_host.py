@@ -246,3 +246,27 @@ def test_the_query_refuses_like_the_entry_point(knobs):
     assert ask(num_starts=17, batch=1) == (-2, "lbfgsb_minimize: batch mode needs num_starts <= 16 in one workgroup")
     assert ask(cus=0)[0] == -1 and ask(n_out=20)[0] == -1
     assert ask(desc=make(DUMP_NETS["2-16-16-2"])) == (-1, "lbfgsb_minimize: the last Dense layer must have 1 unit")
+
+
+def test_the_fused_kernels_restart_plans(knobs):
+    """The batch-mode plans (a loop's restarts in one workgroup of four waves: what the fused loop kernel's restart phase
+    and the asynchronous launch chain run) that tests/test_gpu_fused_options.py picks its maxcor and num_starts by: bytes
+    of LDS, and where the plan stops taking the request."""
+    def lds_bytes(desc, num_starts, maxcor, n_models=6):
+        _, rc, out = plans(desc, [(n_models, num_starts, maxcor, 256, 1, 0)])
+        f = dict(zip(FIELDS, out[0].tolist()))
+        if rc[0]:
+            assert rc[0] == -2
+            return None
+        assert (f["blocks"], f["waves"], f["PB"]) == (1, 4, num_starts) and f["flavour"] > 0, f
+        return 4 * f["lds_floats"]
+    small, plugin = make(DUMP_NETS["2-16-16-1"]), make(DUMP_NETS["16-32-32-32-1"])
+    # 2->16-16-1, three restarts: 29 is the largest maxcor -- a whole CU's LDS, one loop per CU
+    assert {m: lds_bytes(small, 3, m) for m in (3, 5, 10, 12, 13, 17, 29, 30)} == {
+        3: 8256, 5: 11904, 10: 26832, 12: 35184, 13: 39936, 17: 62016, 29: 160512, 30: None}
+    assert lds_bytes(small, 16, 10) == 123200
+    assert lds_bytes(small, 8, 17) == 157696 and lds_bytes(small, 8, 18) is None        # the edge of that plan
+    # 16->32-32-32-1, five restarts: 19 is the largest
+    assert {m: lds_bytes(plugin, 5, m, 5) for m in (5, 17, 19, 20)} == {5: 39008, 17: 135968, 19: 159968, 20: None}
+    assert lds_bytes(plugin, 1, 5, 5) == 20096 and lds_bytes(plugin, 16, 5, 5) == 92240
+    assert all(b <= LDS_BYTES for b in (160512, 159968))

@@ -90,3 +90,27 @@ def test_an_unknown_compute_is_make_descs_value_error(cls):
 def test_the_sharded_engine_hands_its_keywords_on():
     p = inspect.signature(ShardedEngine.__init__).parameters
     assert p["kw"].kind is inspect.Parameter.VAR_KEYWORD
+
+
+@pytest.mark.parametrize("cls", [NativeEngine, ReplicaEngine])
+def test_the_python_engines_take_a_box(cls):
+    p = inspect.signature(cls.__init__).parameters
+    assert p["low"].default is None and p["high"].default is None
+
+
+@pytest.mark.parametrize("bad", [dict(low=(0.0, 1.0), high=(1.0, 0.5)), dict(low=(0.0, np.nan)), dict(high=(np.inf, 1.0)),
+                                 dict(low=(-np.inf, 0.0)), dict(low=(0.0,)), dict(high=(1.0, 1.0, 1.0)), dict(low=0.0)])
+def test_a_bad_box_is_a_value_error_before_any_device_call(bad):
+    """low > high, a non-finite bound, a wrong length: refused by all three engines (ShardedEngine hands its keywords
+    on) before anything touches a device."""
+    for make in (NativeEngine, ReplicaEngine, lambda ids, **kw: ShardedEngine(ids, shards=2, **kw)):
+        with pytest.raises(ValueError, match="low|high"):
+            make(np.arange(4), device="cpu", **bad)
+
+
+def test_the_box_is_the_unit_box_by_default_and_admits_a_fixed_coordinate():
+    from bore_amd.engine import box
+    lo, hi = box(None, None, 3)
+    assert np.array_equal(lo, np.zeros(3)) and np.array_equal(hi, np.ones(3)) and lo.dtype == hi.dtype == np.float64
+    lo, hi = box([-5, 0.5], (10, 0.5), 2)
+    assert np.array_equal(lo, [-5.0, 0.5]) and np.array_equal(hi, [10.0, 0.5])

@@ -321,9 +321,11 @@ def test_the_dimensions_edges(gpu, knobs, D, maxcor):
     check(("edge", D), maxcor, 5, streamed=True)
 
 
-# ---- the engine: the fused and batch-mode path takes maxcor from the same options -----------------------------------
+# ---- the engines take maxcor from the same options: the lock-step chain, and the fused loop kernel -----------------------
 @pytest.mark.parametrize("maxcor", [5, 17])
 def test_native_engine_equals_python_engine_at_other_maxcor(gpu, knobs, maxcor):
+    """NativeEngine on the lock-step schedule (groups=3: the stand-alone kernels) and on the asynchronous one (the fused
+    loop kernel, whose restart phase is planned in batch mode: one workgroup per loop) against ReplicaEngine."""
     from bore_amd.engine import NativeEngine, ReplicaEngine
     kw = dict(epochs=20, num_samples=64, deduplicate=True, options=dict(maxiter=1000, ftol=1e-9, maxcor=maxcor))
     a = NativeEngine(np.arange(3, 14), groups=3, **kw)
@@ -336,3 +338,14 @@ def test_native_engine_equals_python_engine_at_other_maxcor(gpu, knobs, maxcor):
     th, m, v, t = a.state()
     assert np.array_equal(th, b.theta.cpu().numpy()) and np.array_equal(v, b.adam_v.cpu().numpy())
     assert a.take_stats()["n_fg_rows"] == b.stats["n_fg_rows"]
+    f = NativeEngine(np.arange(3, 14), async_loops=True, **kw)
+    f.run(6)
+    Xf, yf = f.observations()
+    assert np.array_equal(Xf, b.X) and np.array_equal(yf, b.y)
+    th, m, v, t = f.state()
+    assert np.array_equal(th, b.theta.cpu().numpy()) and np.array_equal(v, b.adam_v.cpu().numpy())
+    st = f.take_stats()
+    assert st["fit_ms"] == 0.0 and st["phase_iterations"] == 11 * 6          # the fused kernel ran
+    assert st["n_fg_requests"] == b.stats["n_fg_rows"]                        # (n_fg_rows: less what the image shortcut served)
+    for eng in (a, f):
+        eng.close()
