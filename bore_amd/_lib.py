@@ -33,13 +33,24 @@ STREAM_MAX_SAMPLES = 16384   # include/bore_hip.h BORE_STREAM_MAX_SAMPLES
 
 ACT = dict(linear=0, relu=1, elu=2, sigmoid=3, tanh=4)
 TRANSFORM = dict(identity=0, sigmoid=1, exp=2)
+WEIGHTING = dict(ei=1, lfbo=2)   # include/bore_hip.h BORE_WEIGHTING_*
+WEIGHTING_NORMALIZE = 0x100
+
+
+def weighting_code(weighting, normalize=True):
+    """``None | "ei" | "lfbo"`` (+ ``normalize``) as bore_lfbo_labels' / bore_engine_cfg's int: 0 for None."""
+    if weighting is None:
+        return 0
+    if weighting not in WEIGHTING:
+        raise ValueError(f"weighting must be None or one of {tuple(WEIGHTING)} (got {weighting!r})")
+    return WEIGHTING[weighting] | (WEIGHTING_NORMALIZE if normalize else 0)
 
 # every symbol include/bore_hip.h declares (tests check the .so exports them all)
 EXPORTS = [
     "bore_abi_version", "bore_source_digest", "bore_last_error", "bore_param_count", "bore_mlp_forward",
     "bore_mlp_value_and_input_grad", "bore_mlp_fit", "bore_mlp_evaluate",
     "bore_mlp_fit_weighted", "bore_mlp_evaluate_weighted",
-    "bore_shuffle_perm", "bore_labels", "bore_uniform_candidates", "bore_screen_topk", "bore_sample_screen_topk",
+    "bore_shuffle_perm", "bore_labels", "bore_lfbo_labels", "bore_uniform_candidates", "bore_screen_topk", "bore_sample_screen_topk",
     "bore_lbfgsb_minimize", "bore_lbfgsb_plan_query", "bore_append_observations", "bore_select_best",
     "bore_svgd_optimize", "bore_set_batch", "bore_engine_create", "bore_engine_run", "bore_engine_size", "bore_engine_observations",
     "bore_engine_state", "bore_engine_get_stats", "bore_engine_destroy", "bore_objective_branin01",
@@ -93,7 +104,7 @@ class EngineCfg(C.Structure):
                 ("gamma", C.c_double), ("adam", AdamCfg), ("lbfgsb", LbfgsbOpts),
                 ("low", C.POINTER(C.c_double)), ("high", C.POINTER(C.c_double)),
                 ("resident_wait_us", C.c_int32), ("worker_streams", C.c_int32), ("work_queue", C.c_int32),
-                ("reserved", C.c_int32)]
+                ("weighting", C.c_int32)]
 
 
 class EngineStats(C.Structure):
@@ -226,6 +237,7 @@ def lib():
     L.bore_mlp_evaluate_weighted.argtypes = [dp, i32, vp, vp, vp, vp, i64, vp, vp, vp]
     L.bore_shuffle_perm.argtypes = [u64, i64, i32, i64, i32, i64, vp, vp]
     L.bore_labels.argtypes = [i32, vp, i64, C.c_double, vp, vp, vp]
+    L.bore_lfbo_labels.argtypes = [i32, vp, i64, C.c_double, i32, vp, vp, vp, vp]
     dpp = C.POINTER(C.c_double)
     L.bore_uniform_candidates.argtypes = [u64, i64, i32, i64, i64, i32, dpp, dpp, vp, vp]
     L.bore_screen_topk.argtypes = [dp, i32, vp, vp, i64, i32, i32, vp, vp, vp, vp]

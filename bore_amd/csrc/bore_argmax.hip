@@ -92,6 +92,109 @@ extern "C" int bore_labels(int n_models, const double *y, int64_t N, double gamm
 }
 
 // ---------------------------------------------------------------------------
+// LFBO labels: tau as above, u = max(tau - y, 0), and from u the target z and the row weight w of the weighted fit
+// (include/bore_hip.h: bore_lfbo_labels; bore_amd/data.py lfbo_targets is the numpy statement, bit for bit)
+// ---------------------------------------------------------------------------
+// A sibling of labels_body, not a flag on it: that body is also the fused iteration kernel's first phase.  No batch
+// mode here.  tau: labels_body's statements.  fp64 throughout, one rounding to float32 at the store.
+__global__ __launch_bounds__(BORE_THREADS) void lfbo_labels_kernel(const double *y, int N, double vi, int mode,
+                                                                   int normalize, float *z, float *w,
+                                                                   double *tau_out) {
+  extern __shared__ float smem[];
+  double *ys = reinterpret_cast<double *>(smem);  // [N] + 2 (a, b) | part [BORE_THREADS] | cnt [BORE_THREADS]
+  double *part = ys + N + 2;
+  int *cnt = reinterpret_cast<int *>(part + BORE_THREADS);
+  const int tid = threadIdx.x;
+  const long long model = blockIdx.x;
+  const double *ym = y + model * N;
+  for (int i = tid; i < N; i += BORE_THREADS) ys[i] = ym[i];
+  int lo, hi;
+  if (vi >= (double)(N - 1)) {
+    lo = hi = N - 1;
+  } else if (vi < 0.0) {
+    lo = hi = 0;
+  } else {
+    lo = (int)floor(vi);
+    hi = lo + 1;
+  }
+  const double gam = (vi >= (double)(N - 1)) ? vi - (-1.0) : (vi < 0.0 ? vi : vi - floor(vi));
+  __syncthreads();
+  for (int i = tid; i < N; i += BORE_THREADS) {
+    const double yi = ys[i];
+    int r = 0;
+    for (int j = 0; j < N; ++j) {
+      const double yj = ys[j];
+      r += (yj < yi) || (yj == yi && j < i);
+    }
+    if (r == lo) ys[N] = yi;
+    if (r == hi) ys[N + 1] = yi;
+  }
+  __syncthreads();
+  const double a = ys[N], b = ys[N + 1];
+  const double diff = b - a;
+  double tau = a + diff * gam;
+  if (gam >= 0.5) tau = b - diff * (1.0 - gam);
+  // ubar = (sum of u over the positives) / n_pos in ONE order: thread t adds rows t, t + 256, ... as they come, then
+  // the partial sums are halved, p[t] += p[t + h], h = 128 ... 1
+  bool divide = false;
+  double ubar = 1.0;
+  if (normalize) {
+    double s = 0.0;
+    int c = 0;
+    for (int i = tid; i < N; i += BORE_THREADS) {
+      const double yi = ys[i];
+      if (yi < tau) {
+        s = s + (tau - yi);
+        ++c;
+      }
+    }
+    part[tid] = s;
+    cnt[tid] = c;
+    __syncthreads();
+    for (int h = BORE_THREADS / 2; h > 0; h >>= 1) {
+      if (tid < h) {
+        part[tid] = part[tid] + part[tid + h];
+        cnt[tid] += cnt[tid + h];
+      }
+      __syncthreads();
+    }
+    divide = cnt[0] > 0;
+    if (divide) ubar = part[0] / (double)cnt[0];
+  }
+  for (int i = tid; i < N; i += BORE_THREADS) {
+    const double yi = ys[i];
+    const bool pos = yi < tau;
+    double u = pos ? tau - yi : 0.0;
+    if (divide) u = u / ubar;
+    float zi, wi;
+    if (mode == BORE_WEIGHTING_EI) {
+      zi = pos ? 1.f : 0.f;
+      wi = pos ? (float)u : 1.f;
+    } else {  // BORE_WEIGHTING_LFBO
+      zi = (float)(u / (1.0 + u));
+      wi = (float)(1.0 + u);
+    }
+    z[model * N + i] = zi;
+    w[model * N + i] = wi;
+  }
+  if (tid == 0 && tau_out) tau_out[model] = tau;
+}
+
+extern "C" int bore_lfbo_labels(int n_models, const double *y, int64_t N, double gamma, int weighting, float *z,
+                                float *w, double *tau, void *stream) {
+  if (n_models < 1 || !y || !z || !w) return fail(BORE_E_INVALID, "lfbo_labels: bad argument");
+  if (const int rc = check_weighting("lfbo_labels", weighting)) return rc;
+  const int mode = weighting & 0xff;
+  if (N < 1 || N > 16384) return fail(BORE_E_UNSUPPORTED, "lfbo_labels: N=%lld outside 1..16384", (long long)N);
+  if (!(gamma >= 0.0 && gamma <= 1.0)) return fail(BORE_E_INVALID, "lfbo_labels: gamma outside [0, 1]");
+  if (g_batch) return fail(BORE_E_UNSUPPORTED, "lfbo_labels: no weighting in batch mode (bore_set_batch)");
+  const double vi = (double)(N - 1) * gamma;
+  const size_t bytes = ((size_t)N + 2 + BORE_THREADS) * 8 + BORE_THREADS * 4;
+  return launch_lds(lfbo_labels_kernel, dim3(n_models), dim3(BORE_THREADS), bytes, stream, y, (int)N, vi, mode,
+                    (weighting & BORE_WEIGHTING_NORMALIZE) ? 1 : 0, z, w, tau);
+}
+
+// ---------------------------------------------------------------------------
 // candidates: X ~ U(low, high) from a counter-based stream
 // ---------------------------------------------------------------------------
 struct BoxArgs {

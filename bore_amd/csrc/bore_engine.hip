@@ -77,6 +77,7 @@ struct Group {
   // device
   double *X_seen = nullptr, *y_seen = nullptr, *y_dense = nullptr;
   float *X32 = nullptr, *z = nullptr;
+  float *w = nullptr;  // row weights [Lg][cap], beside z (cfg.weighting != 0 only)
   double *new_x = nullptr, *new_y = nullptr;
   double *x0 = nullptr, *x = nullptr, *jac = nullptr, *fun = nullptr, *x_best = nullptr;
   int32_t *idx = nullptr, *info = nullptr, *best = nullptr;
@@ -195,11 +196,11 @@ int pin_alloc(T **p, size_t count) {
 int alloc_record(bore_engine *e, Group &g, int64_t cap) {
   const size_t Lg = g.b - g.a, D = e->D;
   double *X = nullptr, *y = nullptr, *yd = nullptr;
-  float *X32 = nullptr, *z = nullptr;
+  float *X32 = nullptr, *z = nullptr, *w = nullptr;
   int rc;
   if ((rc = dev_alloc(&X, Lg * cap * D)) || (rc = dev_alloc(&y, Lg * cap)) ||
       (rc = dev_alloc(&yd, Lg * cap)) || (rc = dev_alloc(&X32, Lg * cap * D)) ||
-      (rc = dev_alloc(&z, Lg * cap)))
+      (rc = dev_alloc(&z, Lg * cap)) || (e->cfg.weighting && (rc = dev_alloc(&w, Lg * cap))))
     return rc;
   if (g.X_seen) {
     HIP_TRY(hipStreamSynchronize(g.stream));
@@ -208,8 +209,9 @@ int alloc_record(bore_engine *e, Group &g, int64_t cap) {
     HIP_TRY(hipMemcpy2D(y, cap * 8, g.y_seen, g.cap * 8, g.n * 8, Lg, hipMemcpyDeviceToDevice));
     (void)hipFree(g.X_seen); (void)hipFree(g.y_seen); (void)hipFree(g.y_dense);
     (void)hipFree(g.X32); (void)hipFree(g.z);
+    if (g.w) (void)hipFree(g.w);
   }
-  g.X_seen = X; g.y_seen = y; g.y_dense = yd; g.X32 = X32; g.z = z;
+  g.X_seen = X; g.y_seen = y; g.y_dense = yd; g.X32 = X32; g.z = z; g.w = w;
   g.cap = cap;
   return 0;
 }
@@ -232,17 +234,23 @@ int enqueue(bore_engine *e, Group &g) {
   if (g.has_new) ++g.n;
   g.has_new = false;
   const int64_t N = g.n;
-  if ((rc = bore_labels(Lg, g.y_dense, N, c.gamma, g.z, nullptr, sp))) return rc;
+  // (weighting: LFBO's targets and row weights instead of the labels, then the weighted fit -- generic or streamed)
+  if ((rc = c.weighting ? bore_lfbo_labels(Lg, g.y_dense, N, c.gamma, c.weighting, g.z, g.w, nullptr, sp)
+                        : bore_labels(Lg, g.y_dense, N, c.gamma, g.z, nullptr, sp)))
+    return rc;
   float *th = e->theta + (size_t)g.a * e->P, *m = e->adam_m + (size_t)g.a * e->P,
         *v = e->adam_v + (size_t)g.a * e->P;
   HIP_TRY(hipEventRecord(g.ev[0], g.stream));
-  if ((rc = bore_mlp_fit(&e->desc, Lg, th, m, v, e->adam_t + g.a, g.X32, g.z, N, c.epochs,
-                         c.batch_size, nullptr, c.seed, c.loop_id0 + g.a, g.epochs_seen, &c.adam,
-                         nullptr, sp)))
+  if ((rc = c.weighting ? bore_mlp_fit_weighted(&e->desc, Lg, th, m, v, e->adam_t + g.a, g.X32, g.z, g.w, N, c.epochs,
+                                                c.batch_size, nullptr, c.seed, c.loop_id0 + g.a, g.epochs_seen,
+                                                &c.adam, nullptr, sp)
+                        : bore_mlp_fit(&e->desc, Lg, th, m, v, e->adam_t + g.a, g.X32, g.z, N, c.epochs,
+                                       c.batch_size, nullptr, c.seed, c.loop_id0 + g.a, g.epochs_seen, &c.adam,
+                                       nullptr, sp)))
     return rc;
   HIP_TRY(hipEventRecord(g.ev[1], g.stream));
   const int64_t steps = (N + c.batch_size - 1) / c.batch_size;
-  e->st.fit_bytes += (double)Lg * c.epochs * (4.0 * N * (D + 1) + steps * 24.0 * e->P);
+  e->st.fit_bytes += (double)Lg * c.epochs * (4.0 * N * (D + 1 + (c.weighting ? 1 : 0)) + steps * 24.0 * e->P);
   g.epochs_seen += c.epochs;
   if ((rc = e->screen(&e->desc, Lg, th, c.seed, c.loop_id0 + g.a, g.draws, c.num_samples, e->low.data(),
                       e->high.data(), R, g.x0, g.idx, nullptr, sp)))
@@ -1081,7 +1089,7 @@ extern "C" void bore_engine_destroy(bore_engine *e) {
   (void)hipDeviceSynchronize();
   async_destroy(e);
   for (Group &g : e->groups) {
-    free_all({g.X_seen, g.y_seen, g.y_dense, g.X32, g.z, g.new_x, g.x0, g.x, g.jac, g.fun, g.x_best, g.idx},
+    free_all({g.X_seen, g.y_seen, g.y_dense, g.X32, g.z, g.w, g.new_x, g.x0, g.x, g.jac, g.fun, g.x_best, g.idx},
              {g.new_x_pin, g.x_best_pin});
     free_stream(g.stream, g.done, g.ev);
   }
@@ -1114,6 +1122,14 @@ extern "C" int bore_engine_create(const bore_mlp_desc *desc, const bore_engine_c
                 "engine_create: the asynchronous schedule launches in batch mode (bore_set_batch), which the bfloat16 "
                 "fit and the streamed kernels refuse -- run %s network on the lock-step schedule (async_loops = 0)",
                 bf16 ? "a bfloat16" : "a streamed");
+  if (cfg->weighting) {  // (by name, before anything is allocated; the modes: bore_lfbo_labels' own check)
+    if (const int rc = check_weighting("engine_create", cfg->weighting)) return rc;
+    if (cfg->async_loops)
+      return fail(BORE_E_UNSUPPORTED,
+                  "engine_create: weighting needs the lock-step schedule (async_loops = 0): the asynchronous schedule "
+                  "launches in batch mode and its fused kernel takes no sample weights");
+    if (bf16) return fail(BORE_E_UNSUPPORTED, "engine_create: weighting with compute = bfloat16: weighted fits are float32 only");
+  }
   if (bf16 && !bore_shape_is_wide(bore_match_shape(desc))) return fail(BORE_E_UNSUPPORTED, kBf16Shapes);
   if (bf16 && cfg->batch_size != BORE_BATCH_MAX)
     return fail(BORE_E_UNSUPPORTED, kBf16BatchSize, BORE_BATCH_MAX, cfg->batch_size);

@@ -29,7 +29,16 @@ inline int check_transform(const char *who, int transform) {
   return 0;
 }
 
-#define HIP_TRY(expr)                                                                      \
+// The weighting bore_lfbo_labels and the engine take: one mode (BORE_WEIGHTING_*), optionally | BORE_WEIGHTING_NORMALIZE.
+inline int check_weighting(const char *who, int weighting) {
+  const int mode = weighting & 0xff;
+  if ((weighting & ~(0xff | BORE_WEIGHTING_NORMALIZE)) || (mode != BORE_WEIGHTING_EI && mode != BORE_WEIGHTING_LFBO))
+    return fail(BORE_E_INVALID, "%s: unknown weighting 0x%x (BORE_WEIGHTING_EI or BORE_WEIGHTING_LFBO, "
+                "optionally | BORE_WEIGHTING_NORMALIZE)", who, weighting);
+  return 0;
+}
+
+#define HIP_TRY(expr)                                                                     \
   do {                                                                                     \
     hipError_t e_ = (expr);                                                                \
     if (e_ != hipSuccess) return fail(BORE_E_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \

@@ -37,6 +37,13 @@ class Record:
         X, y = self.load_regression_data()
         return X, classification_labels(y, gamma)
 
+    def load_lfbo_data(self, gamma, weighting, normalize=True):
+        """-> X (N, D) float64, z (N,) float32 targets, w (N,) float32 row weights: ``lfbo_targets`` of the record's
+        ``y``, for ``fit(X, z, sample_weight=w)``."""
+        X, y = self.load_regression_data()
+        z, w, _ = lfbo_targets(y, gamma, weighting, normalize)
+        return X, z, w
+
     def is_duplicate(self, x, rtol=1e-5, atol=1e-8):
         """True if ``x`` is allclose to any stored feature vector (the ``filter_fn`` hook of
         ``argmax``: bore/plugins/hpbandster/base.py:210-214)."""
@@ -50,6 +57,52 @@ def classification_labels(y, gamma):
     """z = y < np.quantile(y, gamma)   (bore/data.py:33-34)."""
     y = np.asarray(y)
     return np.less(y, np.quantile(y, q=gamma))
+
+
+LFBO_WEIGHTINGS = ("ei", "lfbo")
+_LFBO_THREADS = 256      # bore_lfbo_labels' workgroup: the order of the sum below is the kernel's
+
+
+def lfbo_targets(y, gamma, weighting, normalize=True):
+    """Targets and row weights of likelihood-free BO (LFBO, Song et al. 2022, expected-improvement utility) for one
+    loop's ``y`` (N,): ``(z, w, tau)`` as float32 / float32 / float64 -- the numpy statement of ``bore_lfbo_labels``,
+    equal to it bit for bit, its summation order included.
+
+    ``tau = np.quantile(y, gamma)``, ``u = tau - y`` where ``y < tau`` (strictly, as ``Record``: ties are negatives)
+    and 0 elsewhere.  ``normalize``: ``u /= mean of u over the positives``, which makes the class balance independent
+    of the objective's units; with no positive nothing is divided and every row is a plain negative.
+
+    ``"ei"``:   ``z = y < tau``, ``w = u`` on the positives and 1 elsewhere (the classifier of BORE with the positives
+                weighted by their improvement).
+    ``"lfbo"``: ``z = u / (1 + u)``, ``w = 1 + u``.  Per row ``w * BCE(f; z) = u * softplus(-f) + softplus(f)``:
+                every row a negative of weight 1 and each positive also a positive of weight u -- LFBO's objective.
+
+    All arithmetic is float64, rounded to float32 once at the end."""
+    if weighting not in LFBO_WEIGHTINGS:
+        raise ValueError(f"weighting must be one of {LFBO_WEIGHTINGS} (got {weighting!r})")
+    y = np.asarray(y, dtype=np.float64).reshape(-1)
+    tau = np.float64(np.quantile(y, q=gamma))
+    pos = np.less(y, tau)
+    u = np.where(pos, tau - y, 0.0)
+    n_pos = int(pos.sum())
+    if normalize and n_pos > 0:
+        # thread t adds u[t], u[t + 256], ... in that order; then p[t] += p[t + h] for h = 128, 64, ..., 1
+        T = _LFBO_THREADS
+        rows = np.zeros((-(-len(u) // T), T))
+        rows.reshape(-1)[:len(u)] = u
+        part = np.zeros(T)
+        for row in rows:
+            part = part + row
+        h = T // 2
+        while h:
+            part[:h] = part[:h] + part[h:2 * h]
+            h //= 2
+        u = u / (part[0] / np.float64(n_pos))
+    if weighting == "ei":
+        z, w = pos.astype(np.float64), np.where(pos, u, 1.0)
+    else:
+        z, w = u / (1.0 + u), 1.0 + u
+    return z.astype(np.float32), w.astype(np.float32), tau
 
 
 def _host_array(a):

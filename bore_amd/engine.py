@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
+from .data import lfbo_targets
 from .optimizers import lockstep
 from .transforms import resolve
 
@@ -101,7 +102,8 @@ class NativeEngine:
                  transform="identity", gamma=0.25, epochs=200, batch_size=64, num_starts=3,
                  num_samples=1024, n_init=10, objective=branin01, options=None, device=None,
                  seed=0, groups=4, deduplicate=False, async_loops=False, resident_wait_us=None,
-                 worker_streams=None, work_queue=None, compute="float32", low=None, high=None):
+                 worker_streams=None, work_queue=None, compute="float32", low=None, high=None, weighting=None,
+                 normalize_utility=True):
         """low, high: the search box, arrays of length input_dim (default: the unit box; ``low[d] == high[d]`` fixes a
         coordinate).  The initial design, the candidates, the restarts' bounds and the fallback draw all take it.
 
@@ -116,8 +118,17 @@ class NativeEngine:
         trajectories, tested.  Needs num_starts <= 16.  Its knobs (None = the library's default; bore_engine_cfg,
         ABI 12 -- environment variables until round 5): ``resident_wait_us`` how long a loop's workgroup waits on its
         CU for the objective value before it parks (0: one launch per loop-iteration), ``worker_streams``,
-        ``work_queue`` False / True: never / always the persistent work-queue launch (default: by size)."""
+        ``work_queue`` False / True: never / always the persistent work-queue launch (default: by size).
+
+        weighting: None (BORE: z = y < tau, the unweighted fit), or "ei" / "lfbo": likelihood-free BO's targets and
+        row weights (``bore_amd.data.lfbo_targets``; ``normalize_utility``: the improvement divided by its mean over
+        the positives) computed on the device from the record, ``bore_lfbo_labels``, and the weighted fit.  Weighted
+        fits run on the generic flavour (also a network with a static-shape kernel, such as 2->16-16-1 or the plugin's
+        16->32-32-32-1) or the streamed one; float32 and the lock-step schedule only -- with ``async_loops=True`` or
+        ``compute="bfloat16"`` the engine raises ``UnsupportedError``."""
         self.low, self.high = box(low, high, int(input_dim))        # (before any device call)
+        self.weighting, self.normalize_utility = weighting, bool(normalize_utility)
+        weighting_code = _lib.weighting_code(weighting, normalize_utility)
         self.device = device or _lib.require_gpu()
         self.loop_ids = np.asarray(loop_ids, dtype=np.int64)
         self.L = L = len(self.loop_ids)
@@ -170,7 +181,7 @@ class NativeEngine:
                              lbfgsb_opts(dict(options or dict(maxiter=1000, ftol=1e-9))), lo_p, hi_p,
                              -1 if resident_wait_us is None else int(resident_wait_us),
                              0 if worker_streams is None else int(worker_streams),
-                             -1 if work_queue is None else int(bool(work_queue)), 0)
+                             -1 if work_queue is None else int(bool(work_queue)), weighting_code)
         self.n_groups = cfg.groups
         th = np.ascontiguousarray(th)
         X0, y0 = np.ascontiguousarray(X0, dtype=np.float64), np.ascontiguousarray(y0, dtype=np.float64)
@@ -355,9 +366,11 @@ class ReplicaEngine:
                  transform="identity", gamma=0.25, epochs=200, batch_size=64, num_starts=3,
                  num_samples=1024, n_init=10, objective=branin01, max_points=None,
                  options=None, device=None, mode="device", seed=0, groups=1, select="device",
-                 deduplicate=False, compute="float32", low=None, high=None):
+                 deduplicate=False, compute="float32", low=None, high=None, weighting=None,
+                 normalize_utility=True):
         """compute, low, high: as ``NativeEngine``'s ("bfloat16": the two wide shapes, batch_size 64; the box:
-        arrays of length input_dim, default the unit box).
+        arrays of length input_dim, default the unit box).  weighting, normalize_utility: as ``NativeEngine``'s
+        (device mode: ``bore_lfbo_labels`` and the weighted fit; the numpy stages: ``data.lfbo_targets``).
 
         mode "device": label, fit, candidate draw, screening and all L-BFGS-B restarts run
         as five launches per BO iteration with ONE host sync (candidates from the device
@@ -383,6 +396,10 @@ class ReplicaEngine:
         self.select, self.deduplicate = select, bool(deduplicate)
         self.mode, self.seed = mode, int(seed)
         self.low, self.high = box(low, high, int(input_dim))        # (before any device call)
+        self.weighting, self.normalize_utility = weighting, bool(normalize_utility)
+        self._weighting_code = _lib.weighting_code(weighting, normalize_utility)
+        if weighting is not None and compute != "float32":
+            raise _lib.UnsupportedError(f"weighting={weighting!r} with compute={compute!r}: weighted fits are float32 only")
         self.device = device or _lib.require_gpu()
         self.loop_ids = np.asarray(loop_ids, dtype=np.int64)
         self.L = L = len(self.loop_ids)
@@ -440,24 +457,29 @@ class ReplicaEngine:
 
     # -- stages ------------------------------------------------------------
     def label(self):
+        """z [L, N]; under a weighting (z, w): each loop's ``data.lfbo_targets``."""
         y = self.groups[0].y
+        if self.weighting is not None:
+            zw = [lfbo_targets(yl, self.gamma, self.weighting, self.normalize_utility) for yl in y]
+            return np.stack([t[0] for t in zw]), np.stack([t[1] for t in zw])
         tau = np.quantile(y, q=self.gamma, axis=1)
         return np.less(y, tau[:, None])
 
-    def fit(self, z):
+    def fit(self, z, w=None):
         L, N, D = self.L, self.N, self.D
         g0 = self.groups[0]
         Xd = torch.from_numpy(g0.X.astype(np.float32)).to(self.device)
         zd = torch.from_numpy(z.astype(np.float32)).to(self.device)
+        wd = None if w is None else torch.from_numpy(np.ascontiguousarray(w, dtype=np.float32)).to(self.device)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         ops.mlp_fit(self.desc, self.theta, self.adam_m, self.adam_v, self.adam_t, Xd, zd,
                     self.epochs, self.batch_size, seed=self.seed,
-                    model_index0=int(self.loop_ids[0]), epoch0=g0.epochs_seen, want_loss=False)
+                    model_index0=int(self.loop_ids[0]), epoch0=g0.epochs_seen, want_loss=False, sample_weight=wd)
         e1.record()
         self._ev.append((e0, e1))
         steps = -(-N // self.batch_size)
-        self.stats["fit_bytes"].append(L * self.epochs * (4 * N * (D + 1) + steps * 24 * self.P))
+        self.stats["fit_bytes"].append(L * self.epochs * (4 * N * (D + 1 + (w is not None)) + steps * 24 * self.P))
         g0.epochs_seen += self.epochs
 
     def screen(self):
@@ -515,6 +537,7 @@ class ReplicaEngine:
             if g.store.n + 1 > g.store.cap:
                 g.store.grow(2 * g.store.cap)
                 g.z_dev = torch.empty(Lg * g.store.cap, dtype=torch.float32, device=self.device)
+                g.w_dev = torch.empty_like(g.z_dev) if self._weighting_code else None
             if g.store.n == N - 1:          # the newest row is still on the host
                 g.new_x_pin_np[:] = g.X[:, -1]
                 g.new_y_pin_np[:] = g.y[:, -1]
@@ -542,19 +565,27 @@ class ReplicaEngine:
             else:
                 g.X_dev[:Lg * N * D].copy_(g.X_pin[:Lg * N * D], non_blocking=True)
                 g.y_dev[:Lg * N].copy_(g.y_pin[:Lg * N], non_blocking=True)
-            _lib.check(lib.bore_labels(Lg, ptr(g.y_dev), N, float(self.gamma), ptr(g.z_dev),
-                                       None, sp))
+            weighted = self._weighting_code != 0
+            if weighted:        # LFBO's targets and row weights instead of the labels
+                _lib.check(lib.bore_lfbo_labels(Lg, ptr(g.y_dev), N, float(self.gamma), self._weighting_code,
+                                                ptr(g.z_dev), ptr(g.w_dev), None, sp))
+            else:
+                _lib.check(lib.bore_labels(Lg, ptr(g.y_dev), N, float(self.gamma), ptr(g.z_dev),
+                                           None, sp))
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-            _lib.check(lib.bore_mlp_fit(C.byref(self.desc), Lg, ptr(th), ptr(m), ptr(v), ptr(t),
-                                        ptr(g.X_dev), ptr(g.z_dev), N, self.epochs,
-                                        self.batch_size, None, C.c_uint64(self.seed),
-                                        int(self.loop_ids[g.a]), g.epochs_seen,
-                                        C.byref(self._adam), None, sp))
+            fit_tail = (N, self.epochs, self.batch_size, None, C.c_uint64(self.seed), int(self.loop_ids[g.a]),
+                        g.epochs_seen, C.byref(self._adam), None, sp)
+            if weighted:
+                _lib.check(lib.bore_mlp_fit_weighted(C.byref(self.desc), Lg, ptr(th), ptr(m), ptr(v), ptr(t),
+                                                     ptr(g.X_dev), ptr(g.z_dev), ptr(g.w_dev), *fit_tail))
+            else:
+                _lib.check(lib.bore_mlp_fit(C.byref(self.desc), Lg, ptr(th), ptr(m), ptr(v), ptr(t),
+                                            ptr(g.X_dev), ptr(g.z_dev), *fit_tail))
             e1.record()
             self._ev.append((e0, e1))
             steps = -(-N // self.batch_size)
-            self.stats["fit_bytes"].append(Lg * self.epochs * (4 * N * (D + 1)
+            self.stats["fit_bytes"].append(Lg * self.epochs * (4 * N * (D + 1 + weighted)
                                                                + steps * 24 * self.P))
             g.epochs_seen += self.epochs
             sample_screen, screen = self._screen
@@ -666,8 +697,10 @@ class ReplicaEngine:
                 g.done.synchronize()
                 outs.append(self._finalize(g))
             return (np.concatenate([o[0] for o in outs]), np.concatenate([o[1] for o in outs]))
-        z = self.label()
-        self.fit(z)
+        if self.weighting is None:
+            self.fit(self.label())
+        else:
+            self.fit(*self.label())
         results = self.restarts(self.screen())
         x_next = self.suggest(results)
         y_next = self.objective(x_next)
@@ -728,6 +761,7 @@ class _Group:
                 self.x_best_pin = torch.empty((Lg, D), dtype=torch.float64).pin_memory()
                 self.best_pin = torch.empty(Lg, dtype=torch.int32).pin_memory()
                 self.z_dev = torch.empty(Lg * self.store.cap, dtype=torch.float32, device=dev)
+                self.w_dev = torch.empty_like(self.z_dev) if eng._weighting_code else None  # (row weights: LFBO only)
             else:
                 self.alloc_inputs(eng, max(256, 2 * self.X.shape[1]))
 
@@ -742,6 +776,7 @@ class _Group:
         self.X_dev = torch.empty(Lg * self.cap * D, dtype=torch.float32, device=dev)
         self.y_dev = torch.empty(Lg * self.cap, dtype=torch.float64, device=dev)
         self.z_dev = torch.empty(Lg * self.cap, dtype=torch.float32, device=dev)
+        self.w_dev = torch.empty_like(self.z_dev) if eng._weighting_code else None  # (row weights: LFBO only)
 
 
 def shard_loop_ids(rank, world_size, loops_per_gpu):

@@ -176,6 +176,25 @@ def labels(y, gamma, want_tau=False):
     return (z, tau) if want_tau else z
 
 
+def lfbo_labels(y, gamma, weighting, normalize=True, want_tau=False):
+    """y [L,N] f64 -> (z [L,N] f32, w [L,N] f32[, tau [L] f64]): LFBO's targets and row weights per model
+    (``bore_lfbo_labels``; ``bore_amd.data.lfbo_targets`` is the numpy statement, equal bit for bit).  ``weighting``
+    "ei" or "lfbo"; ``normalize``: u divided by its mean over the positives."""
+    if weighting is None:
+        raise ValueError("weighting must be 'ei' or 'lfbo' (None is ops.labels)")
+    code = _lib.weighting_code(weighting, normalize)
+    if y.dim() != 2:
+        raise ValueError("y: expected [n_models, N]")
+    L, N = y.shape
+    _chk(y, torch.float64, (L, N), "y")
+    z = torch.empty((L, N), dtype=torch.float32, device=y.device)
+    w = torch.empty((L, N), dtype=torch.float32, device=y.device)
+    tau = torch.empty(L, dtype=torch.float64, device=y.device) if want_tau else None
+    _lib.check(_lib.lib().bore_lfbo_labels(L, _lib.ptr(y), N, float(gamma), code, _lib.ptr(z), _lib.ptr(w),
+                                           _lib.ptr(tau), _lib.stream_ptr()))
+    return (z, w, tau) if want_tau else (z, w)
+
+
 def _host_f64(a, D, name):
     import numpy as np
     a = np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64), (D,)))

@@ -19,7 +19,7 @@ import numpy as np
 from scipy.optimize import Bounds
 
 from ..base import maybe_distort
-from ..data import Record
+from ..data import LFBO_WEIGHTINGS, Record
 from ..layers import BinaryCrossentropy, l2
 from ..math import steps_per_epoch
 from ..models import MaximizableDenseSequential
@@ -32,9 +32,17 @@ class ClassifierSuggester:
                  num_starts=5, num_samples=1024, batch_size=64, num_steps_per_iter=1000,
                  num_epochs_per_iter=None, optimizer="adam", num_layers=2, num_units=32,
                  activation="elu", l2_factor=None, transform="sigmoid", method="L-BFGS-B",
-                 max_iter=1000, ftol=1e-9, distortion=None, seed=None, logger=None, space=None):
+                 max_iter=1000, ftol=1e-9, distortion=None, seed=None, logger=None, space=None,
+                 weighting=None, normalize_utility=True):
         """space: a ``DenseSpace``; then ``bounds`` is its unit box, ``suggest()`` returns a
-        configuration dictionary and ``observe()`` takes one."""
+        configuration dictionary and ``observe()`` takes one.
+
+        weighting: None (BORE, the reference), or "ei" / "lfbo": the classifier of likelihood-free BO -- every update
+        fits on ``Record.load_lfbo_data``'s targets and row weights (``bore_amd.data.lfbo_targets``;
+        ``normalize_utility``: the improvement divided by its mean over the positives)."""
+        if weighting is not None and weighting not in LFBO_WEIGHTINGS:
+            raise ValueError(f"weighting must be None or one of {LFBO_WEIGHTINGS} (got {weighting!r})")
+        self.weighting, self.normalize_utility = weighting, bool(normalize_utility)
         assert (bounds is None) != (space is None), "give either `bounds` or `space`"
         self.space = space
         if space is not None:
@@ -95,9 +103,18 @@ class ClassifierSuggester:
         epochs = self.num_epochs_per_iter
         if epochs is None:
             epochs = self.num_steps_per_iter // num_steps
-        self.logit.fit(X, z, epochs=epochs, batch_size=self.batch_size, callbacks=[],
-                       verbose=False)
-        loss, accuracy = self.logit.evaluate(X, z, verbose=False)
+        if self.weighting is None:
+            self.logit.fit(X, z, epochs=epochs, batch_size=self.batch_size, callbacks=[],
+                           verbose=False)
+            loss, accuracy = self.logit.evaluate(X, z, verbose=False)
+        else:
+            # LFBO: fit on the targets and row weights; log the weighted objective, and the accuracy against the hard
+            # labels (a soft target against 0.5 means nothing)
+            _, zt, w = self.record.load_lfbo_data(self.gamma, self.weighting, self.normalize_utility)
+            self.logit.fit(X, zt, epochs=epochs, batch_size=self.batch_size, callbacks=[],
+                           verbose=False, sample_weight=w)
+            loss, _ = self.logit.evaluate(X, zt, verbose=False, sample_weight=w)
+            _, accuracy = self.logit.evaluate(X, z, verbose=False)
         self.last_fit = (loss, accuracy)
         self.logger.info(f"[Model fit: loss={loss:.3f}, accuracy={accuracy:.3f}] "
                          f"dataset size: {dataset_size}, batch size: {self.batch_size}, "

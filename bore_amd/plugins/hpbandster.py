@@ -73,7 +73,8 @@ class ClassifierConfigGenerator(_GeneratorBase):
             num_samples=optimizer_kws.get("num_samples", 1024),
             method=optimizer_kws.get("method", "L-BFGS-B"),
             ftol=optimizer_kws.get("ftol", 1e-9), max_iter=optimizer_kws.get("max_iter", 1000),
-            distortion=optimizer_kws.get("distortion"), seed=seed, logger=self.logger)
+            distortion=optimizer_kws.get("distortion"), seed=seed, logger=self.logger,
+            weighting=fit_kws.get("weighting"), normalize_utility=fit_kws.get("normalize_utility", True))
         s = self._suggester
         self.gamma, self.num_random_init, self.random_rate = s.gamma, s.num_random_init, s.random_rate
         self.input_dim, self.bounds = s.input_dim, s.bounds
@@ -105,7 +106,9 @@ class BORE(_HyperBand):
                  num_random_init=10, random_rate=0.1, retrain=False, num_starts=5, num_samples=1024,
                  batch_size=64, num_steps_per_iter=1000, num_epochs_per_iter=None, optimizer="adam",
                  num_layers=2, num_units=32, activation="elu", l2_factor=None, transform="sigmoid",
-                 method="L-BFGS-B", max_iter=1000, ftol=1e-9, distortion=None, seed=None, **kwargs):
+                 method="L-BFGS-B", max_iter=1000, ftol=1e-9, distortion=None, seed=None, weighting=None,
+                 normalize_utility=True, **kwargs):
+        """weighting, normalize_utility: ``ClassifierSuggester``'s (None: BORE; "ei" / "lfbo": likelihood-free BO)."""
         if gamma is None:
             gamma = 1 / eta
         cg = ClassifierConfigGenerator(
@@ -114,7 +117,8 @@ class BORE(_HyperBand):
             classifier_kws=dict(num_layers=num_layers, num_units=num_units, l2_factor=l2_factor,
                                 activation=activation, optimizer=optimizer),
             fit_kws=dict(batch_size=batch_size, num_steps_per_iter=num_steps_per_iter,
-                         num_epochs_per_iter=num_epochs_per_iter),
+                         num_epochs_per_iter=num_epochs_per_iter, weighting=weighting,
+                         normalize_utility=normalize_utility),
             optimizer_kws=dict(transform=transform, method=method, max_iter=max_iter, ftol=ftol,
                                distortion=distortion, num_starts=num_starts, num_samples=num_samples),
             seed=seed)
@@ -140,6 +144,13 @@ class BORE(_HyperBand):
 # ------------------------------------------------------------------------------------------------
 # multi-fidelity: bore/plugins/hpbandster/multi_fidelity.py
 # ------------------------------------------------------------------------------------------------
+def _refuse_weighting(weighting):
+    if weighting is not None:
+        from .._lib import UnsupportedError
+        raise UnsupportedError(f"weighting={weighting!r}: the recurrent classifier's kernels take no sample weights "
+                               "(BORE / ClassifierSuggester take a weighting)")
+
+
 class SequenceClassifierConfigGenerator(_GeneratorBase):
     """:95-329.  An LSTM classifier (``StackedRecurrentFactory``) over the rungs of the ladder: the
     many-to-many network is fitted on the label sequences of every configuration, and a one-to-one
@@ -149,6 +160,7 @@ class SequenceClassifierConfigGenerator(_GeneratorBase):
     def __init__(self, config_space, gamma, num_random_init, random_rate, retrain, classifier_kws,
                  fit_kws, optimizer_kws, seed, **kwargs):
         super().__init__(**kwargs)
+        _refuse_weighting(fit_kws.get("weighting"))
         from ..data import MultiFidelityRecord
         from ..layers import l2
         from ..models import StackedRecurrentFactory
@@ -281,7 +293,10 @@ class BOREHyperband(_HyperBand):
                  random_rate=0.1, retrain=False, num_starts=5, num_samples=1024, batch_size=64,
                  num_steps_per_iter=1000, num_epochs=None, optimizer="adam", mask_value=-1., num_layers=2,
                  num_units=32, activation="elu", l2_factor=None, transform="sigmoid", method="L-BFGS-B",
-                 max_iter=1000, ftol=1e-9, distortion=None, seed=None, acquisition="lockstep", **kwargs):
+                 max_iter=1000, ftol=1e-9, distortion=None, seed=None, acquisition="lockstep", weighting=None,
+                 **kwargs):
+        """weighting: anything but None raises ``UnsupportedError`` (the recurrent fits take no sample weights)."""
+        _refuse_weighting(weighting)
         if gamma is None:
             gamma = 1 / eta
         cg = SequenceClassifierConfigGenerator(
