@@ -49,7 +49,7 @@ def weighting_code(weighting, normalize=True):
 EXPORTS = [
     "bore_abi_version", "bore_source_digest", "bore_last_error", "bore_param_count", "bore_mlp_forward",
     "bore_mlp_value_and_input_grad", "bore_mlp_fit", "bore_mlp_evaluate",
-    "bore_mlp_fit_weighted", "bore_mlp_evaluate_weighted",
+    "bore_mlp_fit_weighted", "bore_mlp_evaluate_weighted", "bore_fit_plan_query",
     "bore_shuffle_perm", "bore_labels", "bore_lfbo_labels", "bore_uniform_candidates", "bore_screen_topk", "bore_sample_screen_topk",
     "bore_lbfgsb_minimize", "bore_lbfgsb_plan_query", "bore_append_observations", "bore_select_best",
     "bore_svgd_optimize", "bore_set_batch", "bore_engine_create", "bore_engine_run", "bore_engine_size", "bore_engine_observations",
@@ -235,6 +235,7 @@ def lib():
     L.bore_mlp_fit_weighted.argtypes = [dp, i32, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, vp, u64, i64,
                                         i64, C.POINTER(AdamCfg), vp, vp]
     L.bore_mlp_evaluate_weighted.argtypes = [dp, i32, vp, vp, vp, vp, i64, vp, vp, vp]
+    L.bore_fit_plan_query.argtypes = [dp, i32, i64, i32, i32, i32, i32, C.POINTER(C.c_int32), i32]
     L.bore_shuffle_perm.argtypes = [u64, i64, i32, i64, i32, i64, vp, vp]
     L.bore_labels.argtypes = [i32, vp, i64, C.c_double, vp, vp, vp]
     L.bore_lfbo_labels.argtypes = [i32, vp, i64, C.c_double, i32, vp, vp, vp, vp]

@@ -888,13 +888,18 @@ __device__ __forceinline__ void wide_rounds_f32(const Net &net, const float (&xi
 }
 
 // (the body is a device function so that the fused iteration kernel of bore_iter.hip can run it)
-// WEIGHTED (the generic flavour alone, never batch mode): `sw` holds a sample weight per row, [n_models][N] like z; row
-// i's loss term and d loss / d logit are scaled by sw[i], the divisor of the batch mean stays the row count.  A
-// template flag, so that every other instantiation is the code it was.
+// WEIGHTED (the generic flavour and the narrow static shapes, never batch mode): `sw` holds a sample weight per row,
+// [n_models][N] like z; row i's loss term and d loss / d logit are scaled by sw[i], the divisor of the batch mean
+// stays the row count.  A template flag, so that every other instantiation is the code it was.  On a static shape
+// the weight travels as the label does: beside z in LDS (`o_w`: N floats behind o_z when data_in_lds -- a kernel
+// argument of its own, FitArgs stays as it is), requested and parked a step ahead in the pipelined form.
 template <int SHAPE, int NW = 4, bool WEIGHTED = false>
 __device__ __forceinline__ void fit_body(const FitArgs &a, const long long slot,
-                                         const int it_now = -1, const float *sw = nullptr) {
-  static_assert(!WEIGHTED || (SHAPE == 0 && NW == 4), "sample weights: the generic four-wave flavour");
+                                         const int it_now = -1, const float *sw = nullptr, const int o_w = 0) {
+  static_assert(!WEIGHTED || (NW == 4 && (SHAPE == 0 || bore_flavour_listed(FitWeightedFlavours{}, SHAPE))) ||
+                    (NW == 8 && bore_flavour_listed(FitWeightedW8Flavours{}, SHAPE)),
+                "sample weights: the generic four-wave flavour and the narrow static shapes (four waves: 1, 2, 5, 6, 7; "
+                "eight: 2, 5, 6) -- the wide shapes, the compile-time-depth flavours and wide_rounds_f32 take none");
   extern __shared__ float smem[];
   constexpr MlpLayout Lc = bore_static_layout(SHAPE > 0 ? SHAPE : 0, 1, BORE_BATCH_MAX);
   constexpr bool WIDE = bore_shape_is_wide(SHAPE > 0 ? SHAPE : 0);
@@ -942,6 +947,8 @@ __device__ __forceinline__ void fit_body(const FitArgs &a, const long long slot,
   if (a.data_in_lds) {
     for (int i = tid; i < N * D; i += nthr) smem[a.o_X + i] = X_g[i];
     for (int i = tid; i < N; i += nthr) smem[a.o_z + i] = z_g[i];
+    if constexpr (WEIGHTED && SHAPE > 0)
+      for (int i = tid; i < N; i += nthr) smem[o_w + i] = sw_g[i];
   }
   __syncthreads();
   if (L.any_l2) {  // l2 penalty of the incoming weights (what the first step's loss sees)
@@ -969,6 +976,11 @@ __device__ __forceinline__ void fit_body(const FitArgs &a, const long long slot,
   // loop-invariant addresses instead of the perm -> row -> operand chain.  (The slot is private to
   // its lane: no synchronisation; LDS rather than a register carried around the loop, which the
   // compiler rotated with copies that waited for the request at once.)  Same permutations, same rows.
+  // WEIGHTED: the label plane has a free slot in every lane with q4 != 0 (it parks 0 there); lane 16 + m16 parks the
+  // row's weight in its own, and lane m16 reads that slot beside its label.  The slot is then private to a PAIR of
+  // lanes of one wave, written by one and read by the other: a wave's LDS accesses complete in program order, the
+  // read is a step later than the store, so there is still no synchronisation and no slot more than the unweighted
+  // fit carves.
   // Round 6: the eight-wave kernel too -- its fifth wave never has rows, so every data set of up to 128 rows qualifies;
   // before, it drew the shuffles of two epochs with the whole workgroup at the top of every other epoch: 2.1 k cycles
   // per epoch of 16->32-32-32-1 at N 100, 1.07 k of a 13.5 k-cycle step (profiles/r6/ab_log.txt).
@@ -995,13 +1007,15 @@ __device__ __forceinline__ void fit_body(const FitArgs &a, const long long slot,
   auto request_row = [&](float (&gx)[PRE_KC], float &gz, const int srow) {  // (pipe_perm: the data is in LDS)
 #pragma unroll
     for (int kc = 0; kc < PRE_KC; ++kc) gx[kc] = smem[a.o_X + srow * D + min(4 * kc + q4, D - 1)];
-    gz = smem[a.o_z + srow];
+    if constexpr (WEIGHTED) gz = smem[(q4 == 1 ? o_w : a.o_z) + srow];  // (lanes 16..31: the row's weight)
+    else gz = smem[a.o_z + srow];
   };
   auto park_row = [&](const float (&gx)[PRE_KC], const float gz, const bool live_row) {
 #pragma unroll
     for (int kc = 0; kc < PRE_KC; ++kc)
       stage[kc * BORE_THREADS] = (4 * kc + q4 < D && live_row) ? gx[kc] : 0.f;
-    stage[PRE_KC * BORE_THREADS] = (q4 == 0 && live_row) ? gz : 0.f;
+    if constexpr (WEIGHTED) stage[PRE_KC * BORE_THREADS] = (q4 <= 1 && live_row) ? gz : 0.f;
+    else stage[PRE_KC * BORE_THREADS] = (q4 == 0 && live_row) ? gz : 0.f;
   };
   // Step size of Adam step t: lr * sqrt(1 - beta2^t) / (1 - beta1^t).  Every wave forms the
   // first one; after that the last wave computes the NEXT step's while it waits at the end of
@@ -1080,11 +1094,13 @@ __device__ __forceinline__ void fit_body(const FitArgs &a, const long long slot,
       int src = 0;  // static path: this lane's mini-batch row, requested ahead of the arithmetic below
       bool live_n = false;  // (PIPE: src is the NEXT step's row of this lane, live_n whether it has one)
       float cx[PRE_KC], cz = 0.f;  // (PIPE) this step's row, parked during the last step
+      [[maybe_unused]] float cw = 0.f;  // (PIPE, WEIGHTED) its weight: the label slot of lane 16 + m16 of this wave
       if constexpr (SHAPE > 0) {
         if constexpr (PIPE) {
 #pragma unroll
           for (int kc = 0; kc < PRE_KC; ++kc) cx[kc] = stage[kc * BORE_THREADS];
           cz = stage[PRE_KC * BORE_THREADS];
+          if constexpr (WEIGHTED) cw = smem[a.o_stage + PRE_KC * BORE_THREADS + ((tid & (BORE_THREADS - 1)) ^ 16)];
           const bool last_s = s == steps - 1;
           const int *perm_n = last_s ? perm_all + ((e + 1) & 1) * N : perm_s;
           const int row0n = last_s ? 0 : row0 + a.B;
@@ -1117,11 +1133,13 @@ __device__ __forceinline__ void fit_body(const FitArgs &a, const long long slot,
 #pragma unroll
           for (int kc = 0; kc < Net::KC0; ++kc) xin[kc] = 0.f;
           float zz = 0.f;
+          [[maybe_unused]] float wrow = 0.f;  // (WEIGHTED) the row's sample weight: lanes 0..15 use it, as the label
           float nx[PRE_KC], nz = 0.f;  // (PIPE) the next step's row, on its way
           if constexpr (PIPE) {  // this step's row was parked during the last one; request the next step's
 #pragma unroll
             for (int kc = 0; kc < Net::KC0; ++kc) xin[kc] = cx[kc];
             zz = cz;
+            if constexpr (WEIGHTED) wrow = cw;
             // (opaque here: the row's address is the same expression in the branch of the waves without
             // rows, and hoisted in front of both it waited for `src` before the weight requests above)
             int srow = src;
@@ -1133,11 +1151,15 @@ __device__ __forceinline__ void fit_body(const FitArgs &a, const long long slot,
             for (int kc = 0; kc < Net::KC0; ++kc)
               if (4 * kc + q4 < D && live) xin[kc] = smem[a.o_X + src * D + 4 * kc + q4];
             if (q4 == 0 && live) zz = smem[a.o_z + src];
+            if constexpr (WEIGHTED)
+              if (q4 == 0 && live) wrow = smem[o_w + src];
           } else {
 #pragma unroll
             for (int kc = 0; kc < Net::KC0; ++kc)
               if (4 * kc + q4 < D && live) xin[kc] = X_g[src * D + 4 * kc + q4];
             if (q4 == 0 && live) zz = z_g[src];
+            if constexpr (WEIGHTED)
+              if (q4 == 0 && live) wrow = sw_g[src];
           }
 #pragma unroll
           for (int kc = 0; kc < Net::KC0; ++kc)
@@ -1166,7 +1188,8 @@ __device__ __forceinline__ void fit_body(const FitArgs &a, const long long slot,
           float delta = 0.f;
           if (lane < 16 && live) {
             const float x = net.h[Net::n][0][0];
-            delta = fit_bce(x, zz, a.epoch_loss != nullptr, eloss) * inv_nb;
+            if constexpr (WEIGHTED) delta = (fit_bce_weighted(x, zz, wrow, a.epoch_loss != nullptr, eloss) * inv_nb) * wrow;
+            else delta = fit_bce(x, zz, a.epoch_loss != nullptr, eloss) * inv_nb;
           }
           if (lane < 16) {
             if constexpr (ROUNDS) {
@@ -1486,6 +1509,17 @@ __global__ __launch_bounds__(2 * BORE_THREADS) void fit_kernel_w8(const FitArgs 
 // kernel argument of their own: FitArgs, and with it every other fit kernel's argument block, stays as it is.
 __global__ __launch_bounds__(BORE_THREADS) void fit_weighted_kernel(const FitArgs a, const float *sw) {
   fit_body<0, 4, true>(a, blockIdx.x, -1, sw);
+}
+// The weighted fit of a narrow static shape (FitWeightedFlavours; eight waves: FitWeightedW8Flavours): fit_kernel<S> /
+// fit_kernel_w8<S> with the weights and the place of their LDS copy (FitPlan::o_w) as arguments of their own.
+template <int SHAPE>
+__global__ __launch_bounds__(BORE_THREADS) void fit_weighted_static_kernel(const FitArgs a, const float *sw, const int o_w) {
+  fit_body<SHAPE, 4, true>(a, blockIdx.x, -1, sw, o_w);
+}
+template <int SHAPE>
+__global__ __launch_bounds__(2 * BORE_THREADS) void fit_weighted_static_kernel_w8(const FitArgs a, const float *sw,
+                                                                                  const int o_w) {
+  fit_body<SHAPE, 8, true>(a, blockIdx.x, -1, sw, o_w);
 }
 
 // ---------------------------------------------------------------------------
@@ -2330,16 +2364,29 @@ struct FitPlan {
   int flavour;
   bool fits;  // the network and the shuffle have their place (a.L stands): a refusal after that is the carve's
   bool w8;    // the flavour and the carve admit the eight-wave kernel (fit_wants_w8 has the launch's say)
+  int o_w;    // a weighted plan of a static flavour with data_in_lds: the weights' N floats, behind a.o_z (else 0)
+  int stage_floats;  // the size of the region at a.o_stage
 };
+
+// BORE_FIT_WEIGHTED_STATIC = 0: weighted requests on the generic flavour whatever the network, as before the static
+// kernels took them (A/B, tests that compare the two routes' bits); unset or 1: the static kernels where they exist.
+static bool fit_weighted_static_on() {
+  const char *e = getenv("BORE_FIT_WEIGHTED_STATIC");
+  return !(e && !atoi(e));
+}
 
 // Capacity checks, LDS carve and kernel flavour of a float32 fit: no pointer of the request is looked at, `batch` is
 // the batch mode it runs in (bore_set_batch; nullptr: none).  bore_mlp_streamed and fit_padded ask it on its own.
-// `weighted` (a request with sample weights): flavour 0 whatever the network -- the one LDS kernel that reads them;
-// its carve is the unweighted generic one (the weights are read from memory), so the capacity answers are too.
-static int fit_plan(const bore_mlp_desc *desc, int n_models, int64_t N, int batch_size, bool perm,
-                    const bore_batch *batch, FitPlan &p, bool weighted = false) {
+// `fl`: the flavour to plan for.  `weighted` (a request with sample weights) with fl == 0: the generic weighted kernel,
+// whose carve is the unweighted generic one (the weights are read from memory), so the capacity answers are too.
+// `wstatic`: a weighted request on static flavour fl (FitWeightedFlavours) -- the unweighted carve of that flavour, and
+// N more floats for the weights beside z when the data set lives in LDS (p.o_w; data_in_lds counts them).
+static int fit_plan_for(const bore_mlp_desc *desc, int n_models, int64_t N, int batch_size, bool perm,
+                        const bore_batch *batch, FitPlan &p, const int fl, const bool weighted, const bool wstatic) {
   FitArgs &a = p.a;
   p.fits = false;
+  p.o_w = 0;
+  p.stage_floats = 0;
   if (batch_size < 1) return fail(BORE_E_INVALID, "fit: batch_size must be positive (got %d)", batch_size);
   if (N < 1 || N > (1 << 24)) return fail(BORE_E_INVALID, "fit: N=%lld out of range", (long long)N);
   // a mini-batch of up to 64 rows is one tile (larger ones: 64-row sub-tiles, fit_body); perm
@@ -2347,8 +2394,6 @@ static int fit_plan(const bore_mlp_desc *desc, int n_models, int64_t N, int batc
   const int tile_rows = batch_size < BORE_BATCH_MAX ? batch_size : BORE_BATCH_MAX;
   // (the parked-row slots of fit_body: the narrow static shapes only -- a wide one has no LDS to spare)
   // (the fit-only static shape: not in batch mode -- the fused iteration kernels have no case for it)
-  const int fl = !desc || weighted ? 0 : batch ? bore_kernel_flavour(desc, batch_size == BORE_BATCH_MAX)
-                                               : bore_fit_flavour(desc, batch_size == BORE_BATCH_MAX);
   const size_t stage_f = fl > 0 && !bore_shape_is_wide(fl) ? BORE_FIT_STAGE_FLOATS_OF(fl) : 0;
   const size_t fixed_extra = BORE_BATCH_MAX + 8 + stage_f + BORE_LAYOUT_FLOATS + 12;
   // 32->128-128-1 in float32 with 64-row batches: theta and the 64-row images do not share the LDS;
@@ -2397,6 +2442,7 @@ static int fit_plan(const bore_mlp_desc *desc, int n_models, int64_t N, int batc
   a.o_zt = (int)off; off += BORE_BATCH_MAX;
   a.o_misc = (int)off; off += 8;
   a.o_stage = (int)off; off += stage_f;  // each lane's share of its next-step row (fit_body)
+  p.stage_floats = (int)stage_f;
   const int PG = perm ? 1 : perm_group(N, BORE_THREADS);  // epochs shuffled together (N <= 128)
   size_t perm_f = a.perm_in_lds ? (size_t)PG * N : 0, keys_f = perm ? 0 : (size_t)perm_group_scratch_floats(N, PG);
   // (the pipelined fit of 65..128 rows keeps four epochs' shuffles: fit_body, pipe_perm)
@@ -2429,12 +2475,13 @@ static int fit_plan(const bore_mlp_desc *desc, int n_models, int64_t N, int batc
     a.o_m = (int)off; off += L.P_lds;
     a.o_v = (int)off; off += L.P_lds;
   }
-  const size_t data = (size_t)N * (L.w[0] + 1);
+  const size_t data = (size_t)N * (L.w[0] + 1 + (wstatic ? 1 : 0));  // X, z and a static weighted fit's weights
   a.data_in_lds = (off + tail + data) * 4 <= BORE_LDS_BYTES;
   a.o_X = a.o_z = 0;
   if (a.data_in_lds) {
     a.o_X = (int)off; off += (size_t)N * L.w[0];
     a.o_z = (int)off; off += N;
+    if (wstatic) { p.o_w = (int)off; off += N; }
   }
   // 129..512 rows and a flavour with an eight-wave kernel: a second shuffle buffer (fit_body `ahead`) -- behind
   // everything else and only when it still fits, so that it moves nothing and decides nothing
@@ -2470,8 +2517,25 @@ static int fit_plan(const bore_mlp_desc *desc, int n_models, int64_t N, int batc
   // four weight-gradient tiles whose Adam slots are in LDS
   int tiles = 0;
   for (int l = 1; l <= L.n_layers; ++l) tiles += (L.Np[l - 1] >> 4) * (L.Np[l] >> 4);
-  p.w8 = !batch && bore_flavour_listed(FitW8Flavours{}, shape) && (shape > 0 || (a.state_in_lds && tiles > 4));
+  p.w8 = !batch && bore_flavour_listed(FitW8Flavours{}, shape) && (shape > 0 || (a.state_in_lds && tiles > 4)) &&
+         (!wstatic || bore_flavour_listed(FitWeightedW8Flavours{}, shape));
   return 0;
+}
+
+// The plan of a request.  Unweighted: the flavour of the network.  `weighted`: the same flavour where it has a
+// weighted kernel (FitWeightedFlavours: the narrow static shapes at batch_size 64) and the plan stays on it; wherever
+// the unweighted plan would leave the static flavour (an explicit perm too long for LDS, Adam slots that do not fit)
+// and for every other network, flavour 0 with the unweighted generic carve -- the one other LDS kernel that reads
+// weights -- exactly as before the static kernels took any.  BORE_FIT_WEIGHTED_STATIC = 0: flavour 0 always.
+static int fit_plan(const bore_mlp_desc *desc, int n_models, int64_t N, int batch_size, bool perm,
+                    const bore_batch *batch, FitPlan &p, bool weighted = false) {
+  const int fl = !desc ? 0 : batch ? bore_kernel_flavour(desc, batch_size == BORE_BATCH_MAX)
+                                   : bore_fit_flavour(desc, batch_size == BORE_BATCH_MAX);
+  if (!weighted) return fit_plan_for(desc, n_models, N, batch_size, perm, batch, p, fl, false, false);
+  if (!batch && bore_flavour_listed(FitWeightedFlavours{}, fl) && bore_flavour_on(fl) && fit_weighted_static_on() &&
+      !fit_plan_for(desc, n_models, N, batch_size, perm, batch, p, fl, true, true) && p.flavour == fl)
+    return 0;
+  return fit_plan_for(desc, n_models, N, batch_size, perm, batch, p, 0, true, false);
 }
 
 // Eight waves for a launch whose plan admits them: no more models than CUs, or as BORE_FIT_W8 = 0 / 1 forces (-1: unset).
@@ -2524,7 +2588,8 @@ static int fit_padded(const FitRequest &r, int S, void *stream) {
   const int64_t P = bore_param_count(desc), PS = bore_param_count(&dp);
   {  // (would the static fit take it?  its plan and the request's checks, nothing launched)
     FitPlan p;
-    if (fit_plan(&dp, n_models, N, r.batch_size, r.perm != nullptr, g_batch, p) || p.flavour != S ||
+    if (fit_plan(&dp, n_models, N, r.batch_size, r.perm != nullptr, g_batch, p, r.sample_weight != nullptr) ||
+        p.flavour != S ||
         fit_check_request(p.a.L, r))
       return BORE_E_UNSUPPORTED;
   }
@@ -2585,8 +2650,8 @@ extern "C" int bore_mlp_fit_weighted(const bore_mlp_desc *desc, int n_models, fl
 static int fit_run(const FitRequest &r, void *stream) {
   const bore_mlp_desc *desc = r.desc;
   const int n_models = r.n_models;
-  // A weighted request (sample_weight): the generic flavour or the streamed one and nothing else -- no bfloat16, no
-  // batch mode, no zero-padded detour, no static or eight-wave kernel (fit_plan).
+  // A weighted request (sample_weight): the narrow static kernels (four and eight waves, the zero-padded detour
+  // included), the generic flavour or the streamed one -- no bfloat16, no batch mode, no wide static kernel (fit_plan).
   const bool weighted = r.sample_weight != nullptr;
   if (weighted && desc && desc->compute == BORE_COMPUTE_BF16)
     return fail(BORE_E_UNSUPPORTED, "fit: weighted fits are float32 only (compute = bfloat16 takes no sample_weight)");
@@ -2595,7 +2660,7 @@ static int fit_run(const FitRequest &r, void *stream) {
   if (stream_forced(desc)) return stream_fit(r, stream);
   // (BORE_FIT_PAD = 0: such nets on the generic flavour, as before round 4 -- A/B, tests)
   // (fit_padded leaves a request with a fault of its own, or with nothing to do, to the checks below)
-  if (desc && !g_batch && !weighted && r.batch_size == BORE_BATCH_MAX && !(getenv("BORE_FIT_PAD") && !atoi(getenv("BORE_FIT_PAD")))) {
+  if (desc && !g_batch && r.batch_size == BORE_BATCH_MAX && !(getenv("BORE_FIT_PAD") && !atoi(getenv("BORE_FIT_PAD")))) {
     const int S = bore_pads_to_shape(desc);
     if (S) {
       const int rc = fit_padded(r, S, stream);
@@ -2611,12 +2676,22 @@ static int fit_run(const FitRequest &r, void *stream) {
   // (refused for capacity: the streamed flavour, or its own bound by name)
   if (stream_takes(desc, rc)) return stream_fit(r, stream);
   if (rc) return rc < 0 ? rc : 0;
-  if (weighted)
+  const int forced = getenv("BORE_FIT_W8") ? atoi(getenv("BORE_FIT_W8")) : -1;
+  if (weighted && p.flavour == 0)
     return bore_with_flavour(FlavourList<0>{}, p.flavour, [&](auto) {
       return launch_lds(fit_weighted_kernel, dim3(n_models), dim3(BORE_THREADS), p.lds_floats * 4, stream, p.a,
                         r.sample_weight);
     });
-  const int forced = getenv("BORE_FIT_W8") ? atoi(getenv("BORE_FIT_W8")) : -1;
+  if (weighted && p.w8 && fit_wants_w8(n_models, forced, device_cus()))
+    return bore_with_flavour(FitWeightedW8Flavours{}, p.flavour, [&](auto S) {
+      return launch_lds(fit_weighted_static_kernel_w8<S()>, dim3(n_models), dim3(2 * BORE_THREADS), p.lds_floats * 4,
+                        stream, p.a, r.sample_weight, p.o_w);
+    });
+  if (weighted)
+    return bore_with_flavour(FitWeightedFlavours{}, p.flavour, [&](auto S) {
+      return launch_lds(fit_weighted_static_kernel<S()>, dim3(n_models), dim3(BORE_THREADS), p.lds_floats * 4, stream,
+                        p.a, r.sample_weight, p.o_w);
+    });
   if (p.w8 && fit_wants_w8(n_models, forced, device_cus()))
     return bore_with_flavour(FitW8Flavours{}, p.flavour, [&](auto S) {
       return launch_lds(fit_kernel_w8<S()>, dim3(n_models), dim3(2 * BORE_THREADS), p.lds_floats * 4, stream, p.a);
@@ -2624,6 +2699,28 @@ static int fit_run(const FitRequest &r, void *stream) {
   return bore_with_flavour(FitFlavours{}, p.flavour, [&](auto S) {
     return launch_lds(fit_kernel<S()>, dim3(n_models), dim3(BORE_THREADS), p.lds_floats * 4, stream, p.a);
   });
+}
+
+// What bore_mlp_fit (weighted == 0) or bore_mlp_fit_weighted would plan for a request of these sizes outside batch
+// mode: fit_plan asked with BORE_FIT_WEIGHTED_STATIC and BORE_FIT_W8 read as the entry point reads them and the CU
+// count given.  Host only: no HIP call, no allocation, no pointer of a request.
+extern "C" int bore_fit_plan_query(const bore_mlp_desc *desc, int n_models, int64_t N, int batch_size, int with_perm,
+                                   int weighted, int cus, int32_t *out, int n_out) {
+  if (!desc || !out) return fail(BORE_E_INVALID, "fit_plan_query: null pointer");
+  if (n_out < BORE_FIT_PLAN_FIELDS)
+    return fail(BORE_E_INVALID, "fit_plan_query: out holds fewer than %d fields", BORE_FIT_PLAN_FIELDS);
+  if (cus < 1) return fail(BORE_E_INVALID, "fit_plan_query: cus < 1");
+  if (desc->compute != BORE_COMPUTE_F32) return fail(BORE_E_UNSUPPORTED, "fit_plan_query: float32 fits only");
+  FitPlan p{};
+  if (const int rc = fit_plan(desc, n_models, N, batch_size, with_perm != 0, nullptr, p, weighted != 0)) return rc;
+  const int forced = getenv("BORE_FIT_W8") ? atoi(getenv("BORE_FIT_W8")) : -1;
+  const FitArgs &a = p.a;
+  const long long fields[BORE_FIT_PLAN_FIELDS] = {
+      p.flavour, p.w8 && fit_wants_w8(n_models, forced, cus), (long long)p.lds_floats, a.o_tile, a.o_zt, a.o_misc,
+      a.o_stage, p.stage_floats, a.o_perm, a.o_keys, a.o_g, a.o_m, a.o_v, a.o_X, a.o_z, p.o_w, a.o_perm2, a.total,
+      a.o_layout, a.perm_in_lds, a.state_in_lds, a.data_in_lds, a.perm_ahead, a.L.P_lds, a.L.tile_floats};
+  for (int i = 0; i < BORE_FIT_PLAN_FIELDS; ++i) out[i] = (int32_t)fields[i];
+  return 0;
 }
 
 static int fit_bf16_impl(const FitRequest &r, void *stream) {

@@ -160,7 +160,8 @@ __device__ __forceinline__ long long uniform_i64(long long v) {
 }
 
 // fit_body's `stage`: one slot per work-item and k-chunk of the first layer (static shapes 1, 2: at most two)
-// plus one for the label -- each lane's share of its next-step row (bore_hip.hip, pipe_perm)
+// plus one for the label -- each lane's share of its next-step row (bore_hip.hip, pipe_perm).  A weighted fit parks
+// no more: the row's weight rides in the label plane, in the slot of lane 16 + m16, which the unweighted fit zeroes
 #define BORE_FIT_STAGE_FLOATS (3 * BORE_THREADS)
 // (16->32-32-32-1 and the fit-only shapes -- 16 inputs -- have four k-chunks in their first layer)
 // (2->16-16-1 has one: two slots, which is part of what lets three loops of the fused kernel share a CU's LDS)

@@ -158,6 +158,10 @@ struct FlavourList {};
 using AcqFlavours = FlavourList<1, 2, 3, 4, 5, -1, -2, -3, -4, 0>;  // rows, screening, restarts
 using FitFlavours = FlavourList<1, 2, 3, 4, 5, BORE_FIT_SHAPE_16_32, BORE_FIT_SHAPE_16_16, -1, -2, -3, -4, 0>;
 using FitW8Flavours = FlavourList<2, 5, BORE_FIT_SHAPE_16_32, -1, -2, -3, -4>;  // the eight-wave fit
+// the weighted fit (sample_weight) on a static kernel: the narrow shapes with a register-row-block fit, and those of
+// them that have the eight-wave kernel.  (Flavour 0 has its own weighted kernel; 3, 4 and -1..-4 have none.)
+using FitWeightedFlavours = FlavourList<1, 2, 5, BORE_FIT_SHAPE_16_32, BORE_FIT_SHAPE_16_16>;
+using FitWeightedW8Flavours = FlavourList<2, 5, BORE_FIT_SHAPE_16_32>;
 using WideFlavours = FlavourList<3, 4>;        // bfloat16 kernels, the split screen, the eight-wave restarts
 using NarrowWavesFlavours = FlavourList<2, 5>; // the twelve-wave and the two-per-CU restarts
 using FusedFlavours = FlavourList<1, 5>;       // the fused iteration and work-queue kernels (bore_iter.hip)

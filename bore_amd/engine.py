@@ -123,8 +123,9 @@ class NativeEngine:
         weighting: None (BORE: z = y < tau, the unweighted fit), or "ei" / "lfbo": likelihood-free BO's targets and
         row weights (``bore_amd.data.lfbo_targets``; ``normalize_utility``: the improvement divided by its mean over
         the positives) computed on the device from the record, ``bore_lfbo_labels``, and the weighted fit.  Weighted
-        fits run on the generic flavour (also a network with a static-shape kernel, such as 2->16-16-1 or the plugin's
-        16->32-32-32-1) or the streamed one; float32 and the lock-step schedule only -- with ``async_loops=True`` or
+        fits run on the static kernels of a narrow static-shape network (such as 2->16-16-1 or the plugin's
+        16->32-32-32-1 at batch_size 64), else on the generic flavour or the streamed one; float32 and the lock-step
+        schedule only -- with ``async_loops=True`` or
         ``compute="bfloat16"`` the engine raises ``UnsupportedError``."""
         self.low, self.high = box(low, high, int(input_dim))        # (before any device call)
         self.weighting, self.normalize_utility = weighting, bool(normalize_utility)

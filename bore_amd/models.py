@@ -195,8 +195,9 @@ class Sequential:
 
         ``sample_weight`` ((N,) or (N, 1)) and ``class_weight`` (``{0: a, 1: b}``) as in Keras: a step minimises
         ``sum_i w_i loss_i / rows`` (the divisor is the row count), ``w_i`` the row's sample weight times its class's
-        weight.  A weighted fit runs on the generic kernel flavour (or the streamed one) whatever the network's shape
-        -- 2.4 - 3.5x the time of a static-shape network's unweighted fit, the same bits under unit weights;
+        weight.  A weighted fit of a narrow static-shape network runs on that shape's kernels, in the time of its
+        unweighted fit; every other network on the generic kernel flavour (or the streamed one).  The same bits under
+        unit weights;
         ``UnsupportedError`` for a "mixed_bfloat16" model."""
         self._check_weights_supported(sample_weight=sample_weight, class_weight=class_weight)
         x = np.asarray(x) if not isinstance(x, torch.Tensor) else x

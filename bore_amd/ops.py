@@ -97,8 +97,9 @@ def mlp_fit(desc, theta, m, v, t, X, z, epochs, batch_size, perm=None, seed=0, m
     (desc.compute = bfloat16: mixed precision, include/bore_hip.h enum bore_compute.)
 
     ``sample_weight`` [L,N] f32: a weight per row (``bore_mlp_fit_weighted``: the batch loss is
-    ``sum_i w_i loss_i / rows``); float32 networks on the generic or the streamed flavour, ``UnsupportedError`` with
-    compute = bfloat16.  None: the unweighted fit."""
+    ``sum_i w_i loss_i / rows``); float32 networks, on the kernels the unweighted fit of the same request takes where
+    they are the narrow static ones, else on the generic or the streamed flavour (``fit_plan_query`` tells which);
+    ``UnsupportedError`` with compute = bfloat16.  None: the unweighted fit."""
     L, P = theta.shape
     D = desc.input_dim
     _chk(theta, torch.float32, (L, param_count(desc)), "theta")
@@ -128,6 +129,20 @@ def mlp_fit(desc, theta, m, v, t, X, z, epochs, batch_size, perm=None, seed=0, m
     else:
         _lib.check(_lib.lib().bore_mlp_fit_weighted(*head, _lib.ptr(sample_weight), *tail))
     return loss
+
+
+FIT_PLAN_FIELDS = ("flavour", "w8", "lds_floats", "o_tile", "o_zt", "o_misc", "o_stage", "stage_floats", "o_perm",
+                   "o_keys", "o_g", "o_m", "o_v", "o_X", "o_z", "o_w", "o_perm2", "total", "o_layout", "perm_in_lds",
+                   "state_in_lds", "data_in_lds", "perm_ahead", "P_lds", "tile_floats")   # BORE_FIT_PLAN_FIELDS
+
+
+def fit_plan_query(desc, n_models, N, batch_size, with_perm=False, weighted=False, cus=256):
+    """What ``mlp_fit`` would plan for a float32 request of these sizes (``bore_fit_plan_query``): a dict of
+    ``FIT_PLAN_FIELDS`` -- kernel flavour, eight-wave launch, LDS carve.  A host query: no GPU, nothing launched."""
+    out = (C.c_int32 * len(FIT_PLAN_FIELDS))()
+    _lib.check(_lib.lib().bore_fit_plan_query(C.byref(desc), int(n_models), int(N), int(batch_size), int(bool(with_perm)),
+                                              int(bool(weighted)), int(cus), out, len(FIT_PLAN_FIELDS)))
+    return dict(zip(FIT_PLAN_FIELDS, out))
 
 
 def mlp_evaluate(desc, theta, X, z, sample_weight=None):

@@ -172,12 +172,13 @@ int bore_mlp_fit(const bore_mlp_desc *desc, int n_models, float *theta,
  * epoch loss is sum_i w_i loss_i / N plus the penalty term as above.
  *   sample_weight  device fp32 [n_models][N], one weight per row (a class weight is folded in by the caller:
  *                  w_i times b where z_i = 1, times a otherwise); NULL: exactly the call above
- * Unit weights give the bits of the unweighted fit.  A weighted fit runs on the kernels whose layout is a
- * run-time argument and on no other: the generic flavour for every network that fits one workgroup's LDS -- also
- * one with a compile-time layout above, which the generic flavour fits in 2.4 - 2.6x the static kernel's time at
- * the 32-32-1 widths and 3.5x at 16->32-32-32-1, to the same bits -- and the streamed flavour exactly when the
- * unweighted call would take it.  BORE_E_UNSUPPORTED with compute = bfloat16 ("weighted fits are float32 only"), in batch mode, and for a network neither flavour
- * takes (the unweighted call's message).
+ * Unit weights give the bits of the unweighted fit.  A weighted fit of a narrow network with a compile-time layout
+ * (2->16-16-1, 6->32-32-1, 16->32-32-32-1, 16->32-32-1, 16->16-16-1 at batch_size 64, and the nets the call above
+ * zero-pads onto them) runs on that layout's kernels, four or eight waves as the call above chooses, to the bits of
+ * the generic flavour (BORE_FIT_WEIGHTED_STATIC=0 sends it there: a test hook).  Every other network that fits one
+ * workgroup's LDS -- the wide 16->64-64-64-1 among them -- runs on the generic flavour, and on the streamed flavour
+ * exactly when the unweighted call would take it.  BORE_E_UNSUPPORTED with compute = bfloat16 ("weighted fits are
+ * float32 only"), in batch mode, and for a network neither flavour takes (the unweighted call's message).
  */
 int bore_mlp_fit_weighted(const bore_mlp_desc *desc, int n_models, float *theta,
                           float *adam_m, float *adam_v, int64_t *adam_t, const float *X,
@@ -185,6 +186,25 @@ int bore_mlp_fit_weighted(const bore_mlp_desc *desc, int n_models, float *theta,
                           int batch_size, const int32_t *perm, uint64_t seed,
                           int64_t model_index0, int64_t epoch0, const bore_adam_cfg *adam,
                           float *epoch_loss, void *stream);
+
+/*
+ * What bore_mlp_fit (weighted == 0) or bore_mlp_fit_weighted (!= 0) would plan for a float32 request of these sizes
+ * outside batch mode, as integers (tests: the carve against what the kernels index).  Host only: no HIP call, no
+ * allocation, no pointer of a request; BORE_FIT_WEIGHTED_STATIC and BORE_FIT_W8 are read as the entry point reads
+ * them.  The descriptor is planned as it stands: the zero-padded detour of a net with fewer inputs is the entry
+ * point's (ask for the padded descriptor), and so is the streamed flavour behind a capacity refusal.
+ *   with_perm   != 0: a request with explicit shuffles
+ *   cus         compute units to decide the eight-wave launch for (the entry point asks the device)
+ *   out         int32 [n_out >= BORE_FIT_PLAN_FIELDS]: flavour (a static shape's id, -n_layers, or 0), w8 (the launch
+ *               takes the eight-wave kernel), lds_floats, then the carve in floats: o_tile, o_zt, o_misc, o_stage,
+ *               stage_floats (the size of the region at o_stage), o_perm, o_keys, o_g, o_m, o_v, o_X, o_z, o_w (a
+ *               weighted static plan's copy of the weights; 0: none), o_perm2, total, o_layout, then perm_in_lds,
+ *               state_in_lds, data_in_lds, perm_ahead, P_lds, tile_floats
+ * Returns what the entry point's planning returns (0, or its refusal with its message).
+ */
+#define BORE_FIT_PLAN_FIELDS 25
+int bore_fit_plan_query(const bore_mlp_desc *desc, int n_models, int64_t N, int batch_size,
+                        int with_perm, int weighted, int cus, int32_t *out, int n_out);
 
 /*
  * Keras evaluate(X, z): mean BCE(+l2) and binary accuracy (threshold 0.5 on the

@@ -9,7 +9,8 @@
      is known: the iteration is the host's wall time (perf_counter around run(ITERS), a device synchronize on either
      side), median of 11 after a warm-up run.  Device events give the split: the engine's own fit_ms / argmax_ms are
      HIP events on its streams around its two big kernels.  Under a weighting these static-shape networks fit on the
-     generic flavour; fit_ms says what that costs.
+     weighted instantiations of their static kernels (BORE_FIT_WEIGHTED_STATIC=0 in the environment: on the generic
+     flavour, as before those existed); fit_ms says what the weighting costs.
 Every case runs in a child process of its own under a time limit; the first one that fails ends the run.
 Writes profiles/lfbo/lfbo_time.json (or the path given)."""
 import json
