@@ -696,13 +696,11 @@ extern "C" int bore_lstm_value_and_input_grad(const bore_lstm_desc *desc, int n_
   const size_t bytes = (size_t)A.a.lds_floats * 4;
   rc = allow_lds(lstm_value_grad_kernel, bytes);
   if (rc) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  HIP_TRY(hipMallocAsync((void **)&A.ws, (size_t)n_models * tiles * A.a.ws_floats * 4, st));
-  hipLaunchKernelGGL(lstm_value_grad_kernel, dim3((unsigned)tiles, n_models), dim3(NT), bytes, st, A);
-  const hipError_t e = hipGetLastError();
-  (void)hipFreeAsync(A.ws, st);
-  if (e != hipSuccess) return fail(BORE_E_HIP, "lstm_value_grad_kernel: %s", hipGetErrorString(e));
-  return 0;
+  return with_workspace((size_t)n_models * tiles * A.a.ws_floats, stream, "lstm_value_grad_kernel", [&](float *ws) {
+    A.ws = ws;
+    hipLaunchKernelGGL(lstm_value_grad_kernel, dim3((unsigned)tiles, n_models), dim3(NT), bytes, (hipStream_t)stream, A);
+    return 0;
+  });
 }
 
 extern "C" int bore_lstm_fit(const bore_lstm_desc *desc, int n_models, float *theta, float *adam_m, float *adam_v,
@@ -718,18 +716,14 @@ extern "C" int bore_lstm_fit(const bore_lstm_desc *desc, int n_models, float *th
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   const size_t n_ws = (size_t)n_models * A.a.ws_floats, n_g = (size_t)n_models * A.a.P;
-  float *buf = nullptr;
-  HIP_TRY(hipMallocAsync((void **)&buf, (n_ws + n_g) * 4, st));
-  A.ws = buf;
-  A.gacc = buf + n_ws;
-  hipError_t e = hipMemsetAsync(A.gacc, 0, n_g * 4, st);
-  if (e == hipSuccess) {
+  return with_workspace(n_ws + n_g, stream, "lstm_fit", [&](float *buf) {
+    A.ws = buf;
+    A.gacc = buf + n_ws;
+    const hipError_t e = hipMemsetAsync(A.gacc, 0, n_g * 4, st);
+    if (e != hipSuccess) return fail(BORE_E_HIP, "lstm_fit: %s", hipGetErrorString(e));
     hipLaunchKernelGGL(lstm_fit_kernel, dim3(n_models), dim3(NT), bytes, st, A);
-    e = hipGetLastError();
-  }
-  (void)hipFreeAsync(buf, st);
-  if (e != hipSuccess) return fail(BORE_E_HIP, "lstm_fit: %s", hipGetErrorString(e));
-  return 0;
+    return 0;
+  });
 }
 
 extern "C" int bore_lstm_evaluate(const bore_lstm_desc *desc, int n_models, const float *theta, const float *X,

@@ -434,34 +434,14 @@ __global__ void __launch_bounds__(NTH) lstm_stream_screen_pred_kernel(const SScr
   }
 }
 
-// Restarts: bound-constrained L-BFGS-B (lbfgsb.h) around tile_value_grad, stream_lbfgsb_kernel's scheme.  Grid
-// (model, workgroups of the model); one problem per wave at a time, all 64 lanes on it (lbfgsb::Coop); wave w of
-// workgroup b runs the model's problems (b + k gridDim.y) * waves + w, k = 0, 1, .. one after another.  A ROUND:
-// every wave with a live problem advances its state machine to the next request for f and g (reporting finished
-// problems and taking the next on the way) and writes the fp64 point into ITS row of the workgroup's point buffer
-// (behind the tile's workspace); the requests are OR-ed through LDS behind ONE barrier into one workgroup-uniform
-// value, and while that is non-zero every wave, with or without a problem, runs ONE tile_value_grad over the `waves`
-// rows -- tile_forward and tile_backward are full of barriers -- and then takes f and g of its row.  Rows that never
-// asked hold zeros, rows of waves without a request their last point: finite, and no row's bits depend on its
-// neighbours.  The State rests in LDS over the pass (the products want the registers); the optimiser's vectors stay
-// in LDS; points, values and gradients cross global memory between waves of ONE workgroup, handed over by
-// __syncthreads().  No workgroup waits for another; no float atomics.
+// Restarts: bore_stream.hip's stream_restart_drive (the scheme is told there) around tile_value_grad.  This flavour
+// plugs in: the points as fp64 rows of a buffer behind the tile's workspace (tile_begin rounds them to fp32), ONE
+// tile_value_grad over the `waves` rows, f from the values behind the points and g from the tile's dx.
 struct SLbfgsbArgs {
   SLay y;
   const float *theta;
-  const double *x0;
-  double *x, *fun, *jac;
-  int *info;
-  BoxArgs box;
-  int nbd[BORE_DIM_MAX];
-  lbfgsb::Options opt;
-  int R, T, transform, waves;  // waves: how many of the four hold a problem (the workspaces that fit LDS)
-  long long max_rounds;
-  float sign;
-  float *ws;
-  long long ws_stride;  // floats per workgroup: the tile's workspace | fp64 points [4][D] | values [4]
-  // dynamic LDS (float offsets from its 16-byte aligned start): box | vote | per wave: State, fp64, int workspaces
-  int o_box, o_vote, o_prob, prob_floats, o_dw, o_iw;
+  bore::RestartArgs r;  // (ws_stride: the tile's workspace | fp64 points [4][D] | values [4])
+  int T;
 };
 
 constexpr int LB_WAVES = NTH / 64;
@@ -469,103 +449,35 @@ constexpr int LB_WAVES = NTH / 64;
 __global__ void __launch_bounds__(NTH) lstm_stream_lbfgsb_kernel(const SLbfgsbArgs a) {
   __shared__ StreamLds S;
   __shared__ int rows[ROWS];
-  extern __shared__ float smem[];
   const SLay &y = a.y;
-  const int tid = threadIdx.x;
-  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   const long long model = blockIdx.x;
-  const int D = y.a.D, NW = a.waves;
+  const int D = y.a.D, NW = a.r.waves;
   const float *th = a.theta + model * y.a.P;
-  float *ws = a.ws + (model * gridDim.y + blockIdx.y) * a.ws_stride;
+  float *ws = a.r.ws + (model * gridDim.y + blockIdx.y) * a.r.ws_stride;
   double *pts = reinterpret_cast<double *>(ws + y.ws_floats);  // (ws_floats and ws_stride are multiples of 4 floats)
   float *fval = ws + y.ws_floats + 2 * LB_WAVES * D;
   const float *dx = ws + y.o_dx;
-  // (fp64 LDS reads merge into ds_read_b128: every base on a 16-byte boundary, lbfgsb.h)
-  float *dyn = reinterpret_cast<float *>(reinterpret_cast<char *>(smem) + ((16 - ((size_t)smem & 15)) & 15));
-  double *blo = reinterpret_cast<double *>(dyn + a.o_box), *bhi = blo + ((D + 1) & ~1);
-  int *bnbd = reinterpret_cast<int *>(bhi + ((D + 1) & ~1));
-  int *vote = reinterpret_cast<int *>(dyn + a.o_vote);
-  float *slot = dyn + a.o_prob + (size_t)(wv < NW ? wv : 0) * a.prob_floats;
-  lbfgsb::State *parked = reinterpret_cast<lbfgsb::State *>(slot);
-  const lbfgsb::Work wk = lbfgsb::make_work(reinterpret_cast<double *>(slot + a.o_dw),
-                                            reinterpret_cast<int *>(slot + a.o_iw), D, a.opt.m);
-  const lbfgsb::Coop cp{lane, 64};
-  if (tid < D) {
-    blo[tid] = a.box.lo[tid];
-    bhi[tid] = a.box.hi[tid];
-    bnbd[tid] = a.nbd[tid];
-  }
-  for (int i = tid; i < LB_WAVES * D; i += NTH) pts[i] = 0.0;  // (rows of waves that never ask)
-  for (int b = tid; b < ROWS; b += NTH) rows[b] = b < NW ? b : 0;
   Src<double> src;
   src.X = pts;
   src.row_stride = D;
   src.x_step = 0;
-  __syncthreads();
-
-  lbfgsb::State st;
-  int k = 0;           // problems this wave has taken
-  long long q = 0;     // the live one: x0 / x / fun / jac / info of restart q of the model
-  bool live = false;
-  // the wave's next problem, if the model has one left for it: a zeroed workspace (what the optimiser counts on), init
-  auto take = [&]() {
-    q = ((long long)blockIdx.y + (long long)k * gridDim.y) * NW + wv;
-    ++k;
-    live = wv < NW && q < a.R;
-    if (!live) return;
-    float4 *b4 = reinterpret_cast<float4 *>(slot);
-    for (int i = lane; i < a.prob_floats / 4; i += 64) b4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    bore::wave_lds_sync();
-    lbfgsb::lbfgsb_init(st, wk, D, a.opt.m, a.x0 + (model * a.R + q) * D, blo, bhi, bnbd, cp);
-    bore::wave_lds_sync();
-  };
-  auto report = [&]() {  // bore_lbfgsb_minimize's layout and semantics
-    const long long p = model * a.R + q;
-    for (int d = lane; d < D; d += 64) {
-      a.x[p * D + d] = wk.x[d];
-      a.jac[p * D + d] = wk.g[d];
-    }
-    if (lane == 0) {
-      a.fun[p] = st.f;
-      int *inf = a.info + p * 5;
-      inf[0] = st.nit; inf[1] = st.nfev; inf[2] = st.status; inf[3] = st.task; inf[4] = st.msg;
-    }
-  };
-  take();
-  for (long long round = 0; round < a.max_rounds; ++round) {
-    int need = 0;
-    while (live) {  // (wave-uniform: the 64 lanes hold the same State)
-      const int rc = __builtin_amdgcn_readfirstlane(lbfgsb::lbfgsb_advance<true>(st, wk, blo, bhi, bnbd, a.opt, cp));
-      if (rc == lbfgsb::LB_NEED_FG) {
-        for (int d = lane; d < D; d += 64) pts[wv * D + d] = wk.x[d];
-        need = 1;
-        break;
-      }
-      report();
-      take();
-    }
-    if (need) *parked = st;
-    if (lane == 0) vote[wv] = need;
-    __syncthreads();  // the votes; the points
-    if (!__builtin_amdgcn_readfirstlane(vote[0] | vote[1] | vote[2] | vote[3])) break;  // (ONE value for the workgroup)
-    tile_value_grad(S, y, th, ws, src, rows, NW, a.T, a.transform, a.sign, [&](const int b, const float v) { fval[b] = v; });
-    if (need) {
-      st = *parked;
-      st.f = (double)fval[wv];
-      for (int d = lane; d < D; d += 64) wk.g[d] = (double)dx[wv * D + d];
-      bore::wave_lds_sync();
-    }
-  }
-  // The round cap (cannot happen with a sane cap): what is left is REPORTED, unoptimised, with status 2 -- never dropped.
-  while (live) {
-    if (st.stage != lbfgsb::S_FINISHED) {
-      st.status = 2;
-      st.task = lbfgsb::T_STOP;
-      st.msg = lbfgsb::M_MAXFUN;
-    }
-    report();
-    take();
-  }
+  bore::stream_restart_drive(
+      a.r, D,
+      [&] {
+        for (int i = threadIdx.x; i < LB_WAVES * D; i += NTH) pts[i] = 0.0;  // (rows of waves that never ask)
+        for (int b = threadIdx.x; b < ROWS; b += NTH) rows[b] = b < NW ? b : 0;
+      },
+      [&](const int wv, const int lane, const double *x) {
+        for (int d = lane; d < D; d += 64) pts[wv * D + d] = x[d];
+      },
+      [&] {
+        tile_value_grad(S, y, th, ws, src, rows, NW, a.T, a.r.transform, a.r.sign,
+                        [&](const int b, const float v) { fval[b] = v; });
+      },
+      [&](const int wv, const int lane, double &f, double *g) {
+        f = (double)fval[wv];
+        for (int d = lane; d < D; d += 64) g[d] = (double)dx[wv * D + d];
+      });
 }
 
 struct SFitArgs {
@@ -738,13 +650,12 @@ extern "C" int bore_lstm_stream_forward(const bore_lstm_desc *desc, int n_models
       n_rows, T, many_to_many, mask_value, out);
   if (rc) return rc < 0 ? rc : 0;
   const long long gy = stream_walkers(n_models, (n_rows + bls::ROWS - 1) / bls::ROWS, A.y.ws_floats, true);
-  hipStream_t st = (hipStream_t)stream;
-  HIP_TRY(hipMallocAsync((void **)&A.ws, (size_t)n_models * gy * A.y.ws_floats * sizeof(float), st));
-  hipLaunchKernelGGL(bls::lstm_stream_forward_kernel, dim3(n_models, (unsigned)gy), dim3(bls::NTH), 0, st, A);
-  const hipError_t e = hipGetLastError();
-  (void)hipFreeAsync(A.ws, st);
-  if (e != hipSuccess) return fail(BORE_E_HIP, "lstm_stream_forward_kernel: %s", hipGetErrorString(e));
-  return 0;
+  return with_workspace((size_t)n_models * gy * A.y.ws_floats, stream, "lstm_stream_forward_kernel", [&](float *ws) {
+    A.ws = ws;
+    hipLaunchKernelGGL(bls::lstm_stream_forward_kernel, dim3(n_models, (unsigned)gy), dim3(bls::NTH), 0,
+                       (hipStream_t)stream, A);
+    return 0;
+  });
 }
 
 extern "C" int bore_lstm_stream_value_and_input_grad(const bore_lstm_desc *desc, int n_models, const float *theta,
@@ -757,13 +668,12 @@ extern "C" int bore_lstm_stream_value_and_input_grad(const bore_lstm_desc *desc,
   if (rc) return rc < 0 ? rc : 0;
   A.sign = negate ? -1.f : 1.f;
   const long long gy = stream_walkers(n_models, (n_rows + bls::ROWS - 1) / bls::ROWS, A.y.ws_floats, true);
-  hipStream_t st = (hipStream_t)stream;
-  HIP_TRY(hipMallocAsync((void **)&A.ws, (size_t)n_models * gy * A.y.ws_floats * sizeof(float), st));
-  hipLaunchKernelGGL(bls::lstm_stream_value_grad_kernel, dim3(n_models, (unsigned)gy), dim3(bls::NTH), 0, st, A);
-  const hipError_t e = hipGetLastError();
-  (void)hipFreeAsync(A.ws, st);
-  if (e != hipSuccess) return fail(BORE_E_HIP, "lstm_stream_value_grad_kernel: %s", hipGetErrorString(e));
-  return 0;
+  return with_workspace((size_t)n_models * gy * A.y.ws_floats, stream, "lstm_stream_value_grad_kernel", [&](float *ws) {
+    A.ws = ws;
+    hipLaunchKernelGGL(bls::lstm_stream_value_grad_kernel, dim3(n_models, (unsigned)gy), dim3(bls::NTH), 0,
+                       (hipStream_t)stream, A);
+    return 0;
+  });
 }
 
 extern "C" int bore_lstm_stream_fit(const bore_lstm_desc *desc, int n_models, float *theta, float *adam_m,
@@ -775,13 +685,11 @@ extern "C" int bore_lstm_stream_fit(const bore_lstm_desc *desc, int n_models, fl
       "lstm_stream_fit", A, [&] { return bls::stream_lay(desc, T, bls::WS_FIT, &A.y); }, n_models, theta, adam_m, adam_v,
       adam_t, X, y, N, T, mask_value, epochs, batch_size, perm, adam, epoch_loss);
   if (rc) return rc < 0 ? rc : 0;
-  hipStream_t st = (hipStream_t)stream;
-  HIP_TRY(hipMallocAsync((void **)&A.ws, (size_t)n_models * A.y.ws_floats * sizeof(float), st));
-  hipLaunchKernelGGL(bls::lstm_stream_fit_kernel, dim3(n_models), dim3(bls::NTH), 0, st, A);
-  const hipError_t e = hipGetLastError();
-  (void)hipFreeAsync(A.ws, st);
-  if (e != hipSuccess) return fail(BORE_E_HIP, "lstm_stream_fit_kernel: %s", hipGetErrorString(e));
-  return 0;
+  return with_workspace((size_t)n_models * A.y.ws_floats, stream, "lstm_stream_fit_kernel", [&](float *ws) {
+    A.ws = ws;
+    hipLaunchKernelGGL(bls::lstm_stream_fit_kernel, dim3(n_models), dim3(bls::NTH), 0, (hipStream_t)stream, A);
+    return 0;
+  });
 }
 
 extern "C" int bore_lstm_stream_evaluate(const bore_lstm_desc *desc, int n_models, const float *theta, const float *X,
@@ -797,19 +705,14 @@ extern "C" int bore_lstm_stream_evaluate(const bore_lstm_desc *desc, int n_model
   const long long gy = stream_walkers(n_models, tiles, A.y.ws_floats, true);
   const size_t n_ws = (size_t)n_models * gy * A.y.ws_floats, n_part = (size_t)n_models * tiles * 3;
   hipStream_t st = (hipStream_t)stream;
-  float *buf = nullptr;
-  HIP_TRY(hipMallocAsync((void **)&buf, (n_ws + n_part) * sizeof(float), st));
-  A.ws = buf;
-  A.part = buf + n_ws;
-  hipLaunchKernelGGL(bls::lstm_stream_evaluate_kernel, dim3(n_models, (unsigned)gy), dim3(bls::NTH), 0, st, A);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(bls::lstm_stream_evaluate_finish_kernel, dim3(n_models), dim3(bls::NTH), 0, st, A);
-    e = hipGetLastError();
-  }
-  (void)hipFreeAsync(buf, st);
-  if (e != hipSuccess) return fail(BORE_E_HIP, "lstm_stream_evaluate_kernel: %s", hipGetErrorString(e));
-  return 0;
+  return with_workspace(n_ws + n_part, stream, "lstm_stream_evaluate_kernel", [&](float *buf) {
+    A.ws = buf;
+    A.part = buf + n_ws;
+    hipLaunchKernelGGL(bls::lstm_stream_evaluate_kernel, dim3(n_models, (unsigned)gy), dim3(bls::NTH), 0, st, A);
+    if (hipPeekAtLastError() == hipSuccess)  // (an error stays for the check behind this)
+      hipLaunchKernelGGL(bls::lstm_stream_evaluate_finish_kernel, dim3(n_models), dim3(bls::NTH), 0, st, A);
+    return 0;
+  });
 }
 
 // ---- acquisition: screening and restarts ---------------------------------------------------------------------------
@@ -852,10 +755,10 @@ static int lstm_lbfgsb_request(const char *who, bls::SLbfgsbArgs &A, const bore_
     return rc;
   if (num_starts < 1) return fail(BORE_E_INVALID, "%s: num_starts < 1", who);
   if (!lb || !ub || !opts) return fail(BORE_E_INVALID, "%s: null pointer (bounds, options)", who);
-  if (const int rc = lbfgsb_convert(A.y.a.D, transform, num_starts, lb, ub, opts, A.box, A.nbd, A.opt)) return rc;
+  if (const int rc = lbfgsb_convert(A.y.a.D, transform, num_starts, lb, ub, opts, A.r.box, A.r.nbd, A.r.opt)) return rc;
   if (!theta || !x0 || !x || !fun || !jac || !info) return fail(BORE_E_INVALID, "%s: null pointer", who);
-  A.theta = theta; A.x0 = x0; A.x = x; A.fun = fun; A.jac = jac; A.info = info;
-  A.R = num_starts; A.T = T; A.transform = transform;
+  A.theta = theta; A.r.x0 = x0; A.r.x = x; A.r.fun = fun; A.r.jac = jac; A.r.info = info;
+  A.r.R = num_starts; A.T = T; A.r.transform = transform;
   return 0;
 }
 
@@ -867,33 +770,16 @@ extern "C" int bore_lstm_stream_screen_topk(const bore_lstm_desc *desc, int n_mo
   if (const int rc = lstm_screen_request(who, A, desc, n_models, theta, X_init, n_samples, x_shared, T, num_starts, x0,
                                          idx))
     return rc;
-  int n_pad = 1;
-  while (n_pad < n_samples) n_pad <<= 1;
-  // the predictions: bore_lstm_stream_forward's geometry and workspace rule
-  const long long gy = stream_walkers(n_models, (n_samples + bls::ROWS - 1) / bls::ROWS, A.y.ws_floats, true);
-  hipStream_t st = (hipStream_t)stream;
-  const size_t ws_floats = (size_t)n_models * gy * A.y.ws_floats;
-  const size_t pred_floats = pred ? 0 : (size_t)n_models * n_samples;
-  float *buf = nullptr;
-  HIP_TRY(hipMallocAsync((void **)&buf, (ws_floats + pred_floats) * sizeof(float), st));
-  A.ws = buf;
-  A.out = pred ? pred : buf + ws_floats;
-  // the selection: the Dense flavour's stage, which ranks a prediction buffer and never looks at the network
+  // the predictions: bore_lstm_stream_forward's geometry and workspace rule; the selection: the Dense flavour's stage
   StreamSampleArgs sp;
   sp.sampled = 0; sp.seed = 0; sp.model0 = 0; sp.draw = 0;
-  StreamSelectArgs sel;
-  sel.X = X_init; sel.pred = A.out; sel.x0 = x0; sel.idx = idx;
-  sel.n_samples = n_samples; sel.x_shared = A.x_shared; sel.R = num_starts; sel.n_pad = n_pad; sel.D = A.y.a.D;
-  const size_t key_bytes = 8 * ((size_t)n_pad + 32) + 8;
-  int rc = allow_lds(stream_select_kernel, key_bytes);
-  if (rc == 0) {
-    hipLaunchKernelGGL(bls::lstm_stream_screen_pred_kernel, dim3(n_models, (unsigned)gy), dim3(bls::NTH), 0, st, A);
-    hipLaunchKernelGGL(stream_select_kernel, dim3(n_models), dim3(BORE_THREADS), key_bytes, st, sel, sp);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) rc = fail(BORE_E_HIP, "%s: %s", who, hipGetErrorString(e));
-  }
-  (void)hipFreeAsync(buf, st);
-  return rc;
+  return stream_screen_tail(who, n_models, n_samples, num_starts, A.y.a.D, A.x_shared, X_init, sp, A.y.ws_floats, x0,
+                            idx, pred, stream, [&](float *ws, float *out, long long gy) {
+                              A.ws = ws;
+                              A.out = out;
+                              hipLaunchKernelGGL(bls::lstm_stream_screen_pred_kernel, dim3(n_models, (unsigned)gy),
+                                                 dim3(bls::NTH), 0, (hipStream_t)stream, A);
+                            });
 }
 
 extern "C" int bore_lstm_stream_lbfgsb_minimize(const bore_lstm_desc *desc, int n_models, const float *theta, int T,
@@ -905,45 +791,12 @@ extern "C" int bore_lstm_stream_lbfgsb_minimize(const bore_lstm_desc *desc, int 
   if (const int rc = lstm_lbfgsb_request(who, A, desc, n_models, theta, T, transform, x0, num_starts, lb, ub, opts, x,
                                          fun, jac, info))
     return rc;
-  A.sign = negate ? -1.f : 1.f;
-  // dynamic LDS beside the static panels and rows: the box, the votes, then per wave the parked State and the
-  // optimiser's fp64 and int workspaces -- every region a multiple of 16 bytes (bore_stream_lbfgsb_minimize's carve)
-  const int D = A.y.a.D, De = (D + 1) & ~1;
-  size_t off = 0;
-  A.o_box = 0; off += 4 * (size_t)De + (((size_t)D + 3) & ~(size_t)3);
-  A.o_vote = (int)off; off += 4;
-  A.o_prob = (int)off;
-  const size_t state_f = (sizeof(lbfgsb::State) + 15) / 16 * 4;
-  const size_t dw_f = 2 * (size_t)lbfgsb::dwork_size(D, A.opt.m);
-  const size_t iw_f = ((size_t)lbfgsb::iwork_size(D) + 3) & ~(size_t)3;
-  A.o_dw = (int)state_f;
-  A.o_iw = (int)(state_f + dw_f);
-  A.prob_floats = (int)(state_f + dw_f + iw_f);
-  // (64: the static regions' own alignment and the 16 bytes the kernel may skip to align the dynamic one)
-  const size_t room = (size_t)BORE_LDS_BYTES - sizeof(StreamLds) - bls::ROWS * sizeof(int) - 64 - off * 4;
-  int waves = (int)(room / ((size_t)A.prob_floats * 4));
-  if (waves > bls::LB_WAVES) waves = bls::LB_WAVES;
-  if (waves < 1)
-    return fail(BORE_E_UNSUPPORTED,
-                "%s: one problem's workspace (%zu B at D = %d, maxcor = %d) does not fit the %zu B of LDS beside the "
-                "streamed kernels' panels: lower maxcor", who, (size_t)A.prob_floats * 4, D, A.opt.m, room);
-  A.waves = waves;
-  const size_t lds_bytes = (off + (size_t)waves * A.prob_floats) * 4 + 16;
-  // a model's restarts in groups of `waves`, a workgroup per group -- fewer, each walking several groups, when the
-  // workspaces of all would take more than 64 MiB.  Per workgroup: the value + gradient tile, then the four fp64
-  // points and their four values.
-  A.ws_stride = A.y.ws_floats + 2 * bls::LB_WAVES * D + bls::LB_WAVES;
-  const long long groups = ((long long)num_starts + waves - 1) / waves;
-  const long long gy = stream_walkers(n_models, groups, A.ws_stride, false);  // (the restarts take no CU cap)
-  // every round serves one request of every live problem: a wave's problems, one after another, each within the
-  // optimiser's own limit (lbfgsb_round_cap)
-  A.max_rounds = ((groups + gy - 1) / gy) * lbfgsb_round_cap(opts);
-  hipStream_t st = (hipStream_t)stream;
-  if (const int rc = allow_lds(bls::lstm_stream_lbfgsb_kernel, lds_bytes)) return rc;
-  HIP_TRY(hipMallocAsync((void **)&A.ws, (size_t)n_models * gy * A.ws_stride * sizeof(float), st));
-  hipLaunchKernelGGL(bls::lstm_stream_lbfgsb_kernel, dim3(n_models, (unsigned)gy), dim3(bls::NTH), lds_bytes, st, A);
-  const hipError_t e = hipGetLastError();
-  (void)hipFreeAsync(A.ws, st);
-  if (e != hipSuccess) return fail(BORE_E_HIP, "lstm_stream_lbfgsb_kernel: %s", hipGetErrorString(e));
-  return 0;
+  A.r.sign = negate ? -1.f : 1.f;
+  // static LDS: the panels and the rows.  Per workgroup: the value + gradient tile, then the four fp64 points and
+  // their four values.
+  const int D = A.y.a.D;
+  static_assert(bls::LB_WAVES == BORE_THREADS / 64, "stream_restart_launch's wave limit");
+  return stream_restart_launch(who, "lstm_stream_lbfgsb_kernel", bls::lstm_stream_lbfgsb_kernel, A, D,
+                               sizeof(StreamLds) + bls::ROWS * sizeof(int), n_models,
+                               A.y.ws_floats + 2 * bls::LB_WAVES * D + bls::LB_WAVES, opts, stream);
 }

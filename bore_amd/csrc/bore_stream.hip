@@ -31,6 +31,7 @@
 #include "lbfgsb.h"
 #include "mlp_device.h"
 #include "mlp_math.h"
+#include "stream_restart.h"
 #include "svgd_interact.h"
 
 namespace bore {
@@ -395,22 +396,22 @@ __global__ __launch_bounds__(BORE_THREADS) void stream_select_kernel(const Strea
 }
 
 // ---------------------------------------------------------------------------
-// restarts: bound-constrained L-BFGS-B (lbfgsb.h) around the streamed value + input gradient.  Grid (model, workgroups
-// of the model).  One problem per wave at a time, all 64 lanes on it (lbfgsb::Coop); wave w of workgroup b runs the
-// model's problems (b + k gridDim.y) * waves + w, k = 0, 1, .. one after another.  A ROUND: every wave with a live
-// problem advances its state machine to the next request for f and g (finishing problems and taking the next on the
-// way) and puts the point into ITS row of A_0; then the whole workgroup runs ONE value + gradient pass over the
-// `waves` rows (stream_value_and_grad: the rows kernel's sequence, the same bits), and every wave takes f and g of
-// its row.  stream_gemm is full of barriers, so whether a round's pass runs is ONE workgroup-uniform value -- the
-// waves' requests, OR-ed through LDS behind a barrier -- and every wave, with or without a problem, runs every pass
-// until that value is 0 or the round cap (from maxfun, as lbfgsb_body's) is reached.  Rows of waves without a
-// request keep their last point (zeros at first): finite, and no row's bits depend on its neighbours.  The
-// optimiser's vectors stay in LDS (LB_LANES_SYNC waits for LDS alone); the points, values and gradients cross
-// global memory between waves of ONE workgroup, handed over by __syncthreads().  No workgroup waits for another.
+// restarts: bound-constrained L-BFGS-B (lbfgsb.h) around a streamed value + input gradient pass -- ONE driver,
+// stream_restart_drive, for the Dense kernel below and the recurrent one (bore_lstm_stream.hip).  Grid (model,
+// workgroups of the model).  One problem per wave at a time, all 64 lanes on it (lbfgsb::Coop); wave w of workgroup b
+// runs the model's problems (b + k gridDim.y) * waves + w, k = 0, 1, .. one after another.  A ROUND: every wave with a
+// live problem advances its state machine to the next request for f and g (finishing problems and taking the next on
+// the way) and puts the point into ITS row of the flavour's point buffer (`put`); then the whole workgroup runs ONE
+// value + gradient pass over the `waves` rows (`pass`), and every wave takes f and g of its row (`read`).  The passes
+// are full of barriers, so whether a round's pass runs is ONE workgroup-uniform value -- the waves' requests, OR-ed
+// through LDS behind a barrier -- and every wave, with or without a problem, runs every pass until that value is 0 or
+// the round cap (from maxfun, as lbfgsb_body's) is reached.  Rows of waves without a request keep their last point
+// (zeros at first, from `prepare`, which runs ahead of the first barrier): finite, and no row's bits depend on its
+// neighbours.  The optimiser's vectors stay in LDS (LB_LANES_SYNC waits for LDS alone); the points, values and
+// gradients cross global memory between waves of ONE workgroup, handed over by __syncthreads().  No workgroup waits
+// for another; no float atomics.
 // ---------------------------------------------------------------------------
-struct StreamLbfgsbArgs {
-  MlpLayout L;
-  const float *theta;
+struct RestartArgs {  // what the restart kernels of both flavours take beside their network
   const double *x0;
   double *x, *fun, *jac;
   int *info;
@@ -422,38 +423,35 @@ struct StreamLbfgsbArgs {
   float sign;
   float *ws;
   long long ws_stride;  // floats per workgroup
-  // dynamic LDS (float offsets from its 16-byte aligned start): box | vote | per wave: State, fp64, int workspaces
-  int o_box, o_vote, o_prob, prob_floats, o_dw, o_iw;
+  RestartLds lds;       // the dynamic LDS (stream_restart.h)
 };
 
-__global__ __launch_bounds__(BORE_THREADS) void stream_lbfgsb_kernel(const StreamLbfgsbArgs a) {
-  __shared__ StreamLds S;
+// put(wv, lane, x): the wave's fp64 point x[D] into its row;  pass(): the workgroup's value + gradient pass;
+// read(wv, lane, f, g): f and g[D] of the wave's row.
+template <class Prepare, class Put, class Pass, class Read>
+__device__ __forceinline__ void stream_restart_drive(const RestartArgs &a, const int D, Prepare prepare, Put put,
+                                                     Pass pass, Read read) {
   extern __shared__ float smem[];
-  const MlpLayout &L = stream_begin(S, a.L);
   const int tid = threadIdx.x;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   const long long model = blockIdx.x;
-  const int n = L.n_layers, D = L.w[0], NW = a.waves;
-  const float *th = a.theta + model * L.P;
-  float *ws = a.ws + (model * gridDim.y + blockIdx.y) * a.ws_stride;
-  float *A0 = ws, *An = ws + SROWS * S.pre[n];
-  const float *D0 = ws + SROWS * S.pre[n + 1];
+  const int NW = a.waves;
   // (fp64 LDS reads merge into ds_read_b128: every base on a 16-byte boundary, lbfgsb.h)
   float *dyn = reinterpret_cast<float *>(reinterpret_cast<char *>(smem) + ((16 - ((size_t)smem & 15)) & 15));
-  double *blo = reinterpret_cast<double *>(dyn + a.o_box), *bhi = blo + ((D + 1) & ~1);
+  double *blo = reinterpret_cast<double *>(dyn + a.lds.o_box), *bhi = blo + ((D + 1) & ~1);
   int *bnbd = reinterpret_cast<int *>(bhi + ((D + 1) & ~1));
-  int *vote = reinterpret_cast<int *>(dyn + a.o_vote);
-  float *slot = dyn + a.o_prob + (size_t)(wv < NW ? wv : 0) * a.prob_floats;
+  int *vote = reinterpret_cast<int *>(dyn + a.lds.o_vote);
+  float *slot = dyn + a.lds.o_prob + (size_t)(wv < NW ? wv : 0) * a.lds.prob_floats;
   lbfgsb::State *parked = reinterpret_cast<lbfgsb::State *>(slot);
-  const lbfgsb::Work wk = lbfgsb::make_work(reinterpret_cast<double *>(slot + a.o_dw),
-                                            reinterpret_cast<int *>(slot + a.o_iw), D, a.opt.m);
+  const lbfgsb::Work wk = lbfgsb::make_work(reinterpret_cast<double *>(slot + a.lds.o_dw),
+                                            reinterpret_cast<int *>(slot + a.lds.o_iw), D, a.opt.m);
   const lbfgsb::Coop cp{lane, 64};
   if (tid < D) {
     blo[tid] = a.box.lo[tid];
     bhi[tid] = a.box.hi[tid];
     bnbd[tid] = a.nbd[tid];
   }
-  for (int i = tid; i < BORE_THREADS / 64 * D; i += BORE_THREADS) A0[i] = 0.f;  // (rows of waves that never ask)
+  prepare();
   __syncthreads();
 
   lbfgsb::State st;
@@ -467,7 +465,7 @@ __global__ __launch_bounds__(BORE_THREADS) void stream_lbfgsb_kernel(const Strea
     live = wv < NW && q < a.R;
     if (!live) return;
     float4 *b4 = reinterpret_cast<float4 *>(slot);
-    for (int i = lane; i < a.prob_floats / 4; i += 64) b4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int i = lane; i < a.lds.prob_floats / 4; i += 64) b4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     wave_lds_sync();
     lbfgsb::lbfgsb_init(st, wk, D, a.opt.m, a.x0 + (model * a.R + q) * D, blo, bhi, bnbd, cp);
     wave_lds_sync();
@@ -490,23 +488,22 @@ __global__ __launch_bounds__(BORE_THREADS) void stream_lbfgsb_kernel(const Strea
     while (live) {  // (wave-uniform: the 64 lanes hold the same State)
       const int rc = __builtin_amdgcn_readfirstlane(lbfgsb::lbfgsb_advance<true>(st, wk, blo, bhi, bnbd, a.opt, cp));
       if (rc == lbfgsb::LB_NEED_FG) {
-        for (int d = lane; d < D; d += 64) A0[wv * D + d] = (float)wk.x[d];  // Keras autocast fp64 -> fp32
+        put(wv, lane, wk.x);
         need = 1;
         break;
       }
       report();
       take();
     }
-    // (the State rests in LDS over the pass: stream_gemm wants the registers)
+    // (the State rests in LDS over the pass: the products want the registers)
     if (need) *parked = st;
     if (lane == 0) vote[wv] = need;
-    __syncthreads();  // the votes; the points in A_0
+    __syncthreads();  // the votes; the points
     if (!__builtin_amdgcn_readfirstlane(vote[0] | vote[1] | vote[2] | vote[3])) break;  // (ONE value for the workgroup)
-    stream_value_and_grad(S, L, th, ws, BORE_THREADS / 64, a.transform, a.sign, An, An);  // (A_n: f, then T(sign f))
+    pass();
     if (need) {
       st = *parked;
-      st.f = (double)An[wv];
-      for (int d = lane; d < D; d += 64) wk.g[d] = (double)D0[wv * D + d];
+      read(wv, lane, st.f, wk.g);
       wave_lds_sync();
     }
   }
@@ -520,6 +517,38 @@ __global__ __launch_bounds__(BORE_THREADS) void stream_lbfgsb_kernel(const Strea
     report();
     take();
   }
+}
+
+// The Dense flavour plugs in: the points as float rows of A_0 (Keras autocast), stream_value_and_grad over the four
+// rows (the rows kernel's sequence, the same bits), f from A_n and g from D_0.
+struct StreamLbfgsbArgs {
+  MlpLayout L;
+  const float *theta;
+  RestartArgs r;
+};
+
+__global__ __launch_bounds__(BORE_THREADS) void stream_lbfgsb_kernel(const StreamLbfgsbArgs a) {
+  __shared__ StreamLds S;
+  const MlpLayout &L = stream_begin(S, a.L);
+  const long long model = blockIdx.x;
+  const int n = L.n_layers, D = L.w[0];
+  const float *th = a.theta + model * L.P;
+  float *ws = a.r.ws + (model * gridDim.y + blockIdx.y) * a.r.ws_stride;
+  float *A0 = ws, *An = ws + SROWS * S.pre[n];
+  const float *D0 = ws + SROWS * S.pre[n + 1];
+  stream_restart_drive(
+      a.r, D,
+      [&] {  // (rows of waves that never ask)
+        for (int i = threadIdx.x; i < BORE_THREADS / 64 * D; i += BORE_THREADS) A0[i] = 0.f;
+      },
+      [&](const int wv, const int lane, const double *x) {
+        for (int d = lane; d < D; d += 64) A0[wv * D + d] = (float)x[d];  // Keras autocast fp64 -> fp32
+      },
+      [&] { stream_value_and_grad(S, L, th, ws, BORE_THREADS / 64, a.r.transform, a.r.sign, An, An); },  // (A_n: f, then T(sign f))
+      [&](const int wv, const int lane, double &f, double *g) {
+        f = (double)An[wv];
+        for (int d = lane; d < D; d += 64) g[d] = (double)D0[wv * D + d];
+      });
 }
 
 // ---------------------------------------------------------------------------
@@ -769,26 +798,25 @@ __global__ __launch_bounds__(BORE_THREADS) void stream_fit_kernel(const StreamFi
 // ---------------------------------------------------------------------------
 using namespace bore;
 
-// Within the streamed flavour's bounds?  A predicate: leaves the thread's error string alone.
-static bool stream_within_bounds(const bore_mlp_desc *desc) {
-  MlpLayout L;
-  if (bore_make_layout(desc, 0, BORE_BATCH_MAX, &L) || desc->compute != BORE_COMPUTE_F32) return false;
-  for (int l = 0; l <= L.n_layers; ++l)
-    if (L.w[l] > BORE_STREAM_MAX_UNITS) return false;
-  return true;
-}
-
-// The same as a check: 0, or the error (BORE_E_UNSUPPORTED names the bound).
-static int stream_bounds(const bore_mlp_desc *desc, MlpLayout *L) {
-  if (bore_make_layout(desc, 0, BORE_BATCH_MAX, L)) return fail(BORE_E_INVALID, "bad bore_mlp_desc");
-  if (desc->compute != BORE_COMPUTE_F32) return fail(BORE_E_UNSUPPORTED, kBf16Shapes);
+// Within the streamed flavour's bounds?  0, or the error (BORE_E_UNSUPPORTED names the bound); `quiet`: the code alone,
+// the thread's error string left as it is.
+static int stream_bounds(const bore_mlp_desc *desc, MlpLayout *L, bool quiet = false) {
+  if (bore_make_layout(desc, 0, BORE_BATCH_MAX, L)) return quiet ? BORE_E_INVALID : fail(BORE_E_INVALID, "bad bore_mlp_desc");
+  if (desc->compute != BORE_COMPUTE_F32) return quiet ? BORE_E_UNSUPPORTED : fail(BORE_E_UNSUPPORTED, kBf16Shapes);
   for (int l = 0; l <= L->n_layers; ++l)
     if (L->w[l] > BORE_STREAM_MAX_UNITS)
-      return fail(BORE_E_UNSUPPORTED,
-                  "the model does not fit one workgroup's LDS and %s %d exceeds what the streamed kernels take "
-                  "(BORE_STREAM_MAX_UNITS = %d)",
-                  l ? "a layer width of" : "an input dimension of", L->w[l], BORE_STREAM_MAX_UNITS);
+      return quiet ? BORE_E_UNSUPPORTED
+                   : fail(BORE_E_UNSUPPORTED,
+                          "the model does not fit one workgroup's LDS and %s %d exceeds what the streamed kernels take "
+                          "(BORE_STREAM_MAX_UNITS = %d)",
+                          l ? "a layer width of" : "an input dimension of", L->w[l], BORE_STREAM_MAX_UNITS);
   return 0;
+}
+
+// The same as a predicate.
+static bool stream_within_bounds(const bore_mlp_desc *desc) {
+  MlpLayout L;
+  return stream_bounds(desc, &L, true) == 0;
 }
 
 // BORE_STREAM = 1 (tests, A/B): any float32 request within the bounds takes the streamed flavour.
@@ -827,14 +855,13 @@ static int stream_rows(bool with_grad, const bore_mlp_desc *desc, int n_models, 
   a.ws_stride = (long long)stream_tile_floats(a.L);
   const long long gy = stream_walkers(n_models, (n_rows + SROWS - 1) / SROWS, a.ws_stride, true);
   hipStream_t st = (hipStream_t)stream;
-  HIP_TRY(hipMallocAsync((void **)&a.ws, (size_t)n_models * gy * a.ws_stride * sizeof(float), st));
-  const dim3 grid(n_models, (unsigned)gy);
-  if (with_grad) hipLaunchKernelGGL(stream_rows_kernel<true>, grid, dim3(BORE_THREADS), 0, st, a);
-  else hipLaunchKernelGGL(stream_rows_kernel<false>, grid, dim3(BORE_THREADS), 0, st, a);
-  const hipError_t e = hipGetLastError();
-  (void)hipFreeAsync(a.ws, st);
-  if (e != hipSuccess) return fail(BORE_E_HIP, "streamed rows kernel: %s", hipGetErrorString(e));
-  return 0;
+  return with_workspace((size_t)n_models * gy * a.ws_stride, stream, "streamed rows kernel", [&](float *ws) {
+    a.ws = ws;
+    const dim3 grid(n_models, (unsigned)gy);
+    if (with_grad) hipLaunchKernelGGL(stream_rows_kernel<true>, grid, dim3(BORE_THREADS), 0, st, a);
+    else hipLaunchKernelGGL(stream_rows_kernel<false>, grid, dim3(BORE_THREADS), 0, st, a);
+    return 0;
+  });
 }
 
 static int stream_forward_entry(const bore_mlp_desc *desc, int n_models, const float *theta, const float *X,
@@ -861,14 +888,13 @@ static int stream_evaluate(const bore_mlp_desc *desc, int n_models, const float 
   a.theta = theta; a.X = X; a.z = z; a.loss = loss; a.acc = acc; a.N = N;
   a.ws_stride = (long long)stream_tile_floats(a.L);
   hipStream_t st = (hipStream_t)stream;
-  HIP_TRY(hipMallocAsync((void **)&a.ws, (size_t)n_models * a.ws_stride * sizeof(float), st));
   a.sw = sample_weight;
-  if (sample_weight) hipLaunchKernelGGL(stream_evaluate_kernel<true>, dim3(n_models), dim3(BORE_THREADS), 0, st, a);
-  else hipLaunchKernelGGL(stream_evaluate_kernel<false>, dim3(n_models), dim3(BORE_THREADS), 0, st, a);
-  const hipError_t e = hipGetLastError();
-  (void)hipFreeAsync(a.ws, st);
-  if (e != hipSuccess) return fail(BORE_E_HIP, "streamed evaluate kernel: %s", hipGetErrorString(e));
-  return 0;
+  return with_workspace((size_t)n_models * a.ws_stride, stream, "streamed evaluate kernel", [&](float *ws) {
+    a.ws = ws;
+    if (sample_weight) hipLaunchKernelGGL(stream_evaluate_kernel<true>, dim3(n_models), dim3(BORE_THREADS), 0, st, a);
+    else hipLaunchKernelGGL(stream_evaluate_kernel<false>, dim3(n_models), dim3(BORE_THREADS), 0, st, a);
+    return 0;
+  });
 }
 
 static int stream_fit(const FitRequest &r, void *stream) {
@@ -898,24 +924,18 @@ static int stream_fit(const FitRequest &r, void *stream) {
   a.ws_stride = a.o_g + (batch_size > BORE_BATCH_MAX ? L.P : 0);
   hipStream_t st = (hipStream_t)stream;
   const size_t ws_floats = (size_t)n_models * a.ws_stride;
-  float *buf = nullptr;
-  HIP_TRY(hipMallocAsync((void **)&buf, (ws_floats + perm_ints) * sizeof(float), st));
-  a.ws = buf;
-  int rc = 0;
-  if (!r.perm) {
-    int32_t *drawn = reinterpret_cast<int32_t *>(buf + ws_floats);
-    rc = bore_shuffle_perm(r.seed, r.model_index0, n_models, r.epoch0, epochs, N, drawn, stream);
-    a.perm = drawn;
-  }
-  if (rc == 0) {
+  return with_workspace(ws_floats + perm_ints, stream, "streamed fit kernel", [&](float *buf) {
+    a.ws = buf;
+    if (!r.perm) {
+      int32_t *drawn = reinterpret_cast<int32_t *>(buf + ws_floats);
+      if (const int rc = bore_shuffle_perm(r.seed, r.model_index0, n_models, r.epoch0, epochs, N, drawn, stream)) return rc;
+      a.perm = drawn;
+    }
     a.sw = r.sample_weight;
     if (r.sample_weight) hipLaunchKernelGGL(stream_fit_kernel<true>, dim3(n_models), dim3(BORE_THREADS), 0, st, a);
     else hipLaunchKernelGGL(stream_fit_kernel<false>, dim3(n_models), dim3(BORE_THREADS), 0, st, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) rc = fail(BORE_E_HIP, "streamed fit kernel: %s", hipGetErrorString(e));
-  }
-  (void)hipFreeAsync(buf, st);
-  return rc;
+    return 0;
+  });
 }
 
 extern "C" int bore_mlp_streamed(const bore_mlp_desc *desc) {
@@ -947,6 +967,64 @@ static int stream_acq_bounds(const char *who, const bore_mlp_desc *desc, int n_m
   return 0;
 }
 
+// What the screenings of both flavours run behind their request checks.  ONE buffer: the walkers' workspaces
+// (`ws_stride` floats each, the rows kernels' geometry) and, unless the caller takes them (`pred`), the predictions;
+// launch_pred(ws, out, gy) is the flavour's forward pass over the candidates; the selection is stream_select_kernel,
+// which ranks a prediction buffer and never looks at the network.
+template <class LaunchPred>
+static int stream_screen_tail(const char *who, int n_models, int64_t n_samples, int num_starts, int D, int x_shared,
+                              const double *X_init, const StreamSampleArgs &sp, long long ws_stride, double *x0,
+                              int32_t *idx, float *pred, void *stream, LaunchPred launch_pred) {
+  int n_pad = 1;
+  while (n_pad < n_samples) n_pad <<= 1;
+  // (the rule's clamp to 65535 never binds here: n_samples <= BORE_STREAM_MAX_SAMPLES = 16384 is at most 256 tiles)
+  const long long gy = stream_walkers(n_models, (n_samples + SROWS - 1) / SROWS, ws_stride, true);
+  const size_t ws_floats = (size_t)n_models * gy * ws_stride;
+  const size_t pred_floats = pred ? 0 : (size_t)n_models * n_samples;
+  return with_workspace(ws_floats + pred_floats, stream, who, [&](float *buf) {
+    float *out = pred ? pred : buf + ws_floats;
+    StreamSelectArgs sel;
+    sel.X = X_init; sel.pred = out; sel.x0 = x0; sel.idx = idx;
+    sel.n_samples = n_samples; sel.x_shared = x_shared; sel.R = num_starts; sel.n_pad = n_pad; sel.D = D;
+    const size_t key_bytes = 8 * ((size_t)n_pad + 32) + 8;
+    if (const int rc = allow_lds(stream_select_kernel, key_bytes)) return rc;
+    launch_pred(buf, out, gy);
+    hipLaunchKernelGGL(stream_select_kernel, dim3(n_models), dim3(BORE_THREADS), key_bytes, (hipStream_t)stream, sel, sp);
+    return 0;
+  });
+}
+
+// What the restart entry points of both flavours run behind their request checks, a.r filled but for the geometry:
+// the carve (stream_restart.h) beside `static_bytes` of the kernel's static LDS, the grid, the round cap, the launch
+// around a workspace of `ws_stride` floats per workgroup.
+template <class K, class Args>
+static int stream_restart_launch(const char *who, const char *what, K kernel, Args &a, int D, size_t static_bytes,
+                                 int n_models, long long ws_stride, const bore_lbfgsb_opts *opts, void *stream) {
+  static_assert(STREAM_RESTART_LDS_BYTES == BORE_LDS_BYTES, "stream_restart.h carves another LDS");
+  RestartArgs &r = a.r;
+  RestartCarve c;
+  if (!stream_restart_carve(D, r.opt.m, static_bytes, BORE_THREADS / 64, &c))
+    return fail(BORE_E_UNSUPPORTED,
+                "%s: one problem's workspace (%zu B at D = %d, maxcor = %d) does not fit the %zu B of LDS beside the "
+                "streamed kernels' panels: lower maxcor", who, (size_t)c.lds.prob_floats * 4, D, r.opt.m, c.room);
+  r.lds = c.lds;
+  r.waves = c.waves;
+  // a model's restarts in groups of `waves`, a workgroup per group -- fewer, each walking several groups, when the
+  // workspaces of all would take more than STREAM_WS_BYTES
+  r.ws_stride = ws_stride;
+  const long long groups = ((long long)r.R + c.waves - 1) / c.waves;
+  const long long gy = stream_walkers(n_models, groups, ws_stride, false);  // (the restarts take no CU cap)
+  // every round serves one request of every live problem: a wave's problems, one after another, each within the
+  // optimiser's own limit (lbfgsb_round_cap)
+  r.max_rounds = ((groups + gy - 1) / gy) * lbfgsb_round_cap(opts);
+  if (const int rc = allow_lds(kernel, c.lds_bytes)) return rc;
+  return with_workspace((size_t)n_models * gy * ws_stride, stream, what, [&](float *ws) {
+    r.ws = ws;
+    hipLaunchKernelGGL(kernel, dim3(n_models, (unsigned)gy), dim3(BORE_THREADS), c.lds_bytes, (hipStream_t)stream, a);
+    return 0;
+  });
+}
+
 static int stream_screen(const char *who, const bore_mlp_desc *desc, int n_models, const float *theta,
                          const double *X_init, const SampleSpec *spec, int64_t n_samples, int x_shared, int num_starts,
                          double *x0, int32_t *idx, float *pred, void *stream) {
@@ -964,8 +1042,6 @@ static int stream_screen(const char *who, const bore_mlp_desc *desc, int n_model
     return fail(BORE_E_UNSUPPORTED,
                 "%s: the selection ranks n_samples <= BORE_STREAM_MAX_SAMPLES = %d sort keys in one workgroup's LDS "
                 "(got %lld)", who, BORE_STREAM_MAX_SAMPLES, (long long)n_samples);
-  int n_pad = 1;
-  while (n_pad < n_samples) n_pad <<= 1;
   StreamSampleArgs sp;
   sp.sampled = spec != nullptr;
   sp.seed = 0; sp.model0 = 0; sp.draw = 0;
@@ -980,28 +1056,13 @@ static int stream_screen(const char *who, const bore_mlp_desc *desc, int n_model
   a.theta = theta; a.Xf = nullptr; a.Xd = X_init; a.grad = nullptr;
   a.n_rows = n_samples; a.x_shared = x_shared; a.transform = 0; a.sign = 1.f;
   a.ws_stride = (long long)stream_tile_floats(a.L);
-  // (the rule's clamp to 65535 never binds here: n_samples <= BORE_STREAM_MAX_SAMPLES = 16384 is at most 256 tiles)
-  const long long gy = stream_walkers(n_models, (n_samples + SROWS - 1) / SROWS, a.ws_stride, true);
-  hipStream_t st = (hipStream_t)stream;
-  const size_t ws_floats = (size_t)n_models * gy * a.ws_stride;
-  const size_t pred_floats = pred ? 0 : (size_t)n_models * n_samples;
-  float *buf = nullptr;
-  HIP_TRY(hipMallocAsync((void **)&buf, (ws_floats + pred_floats) * sizeof(float), st));
-  a.ws = buf;
-  a.out = pred ? pred : buf + ws_floats;
-  StreamSelectArgs sel;
-  sel.X = X_init; sel.pred = a.out; sel.x0 = x0; sel.idx = idx;
-  sel.n_samples = n_samples; sel.x_shared = x_shared; sel.R = num_starts; sel.n_pad = n_pad; sel.D = D;
-  const size_t key_bytes = 8 * ((size_t)n_pad + 32) + 8;
-  int rc = allow_lds(stream_select_kernel, key_bytes);
-  if (rc == 0) {
-    hipLaunchKernelGGL(stream_screen_pred_kernel, dim3(n_models, (unsigned)gy), dim3(BORE_THREADS), 0, st, a, sp);
-    hipLaunchKernelGGL(stream_select_kernel, dim3(n_models), dim3(BORE_THREADS), key_bytes, st, sel, sp);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) rc = fail(BORE_E_HIP, "%s: %s", who, hipGetErrorString(e));
-  }
-  (void)hipFreeAsync(buf, st);
-  return rc;
+  return stream_screen_tail(who, n_models, n_samples, num_starts, D, x_shared, X_init, sp, a.ws_stride, x0, idx, pred,
+                            stream, [&](float *ws, float *out, long long gy) {
+                              a.ws = ws;
+                              a.out = out;
+                              hipLaunchKernelGGL(stream_screen_pred_kernel, dim3(n_models, (unsigned)gy),
+                                                 dim3(BORE_THREADS), 0, (hipStream_t)stream, a, sp);
+                            });
 }
 
 extern "C" int bore_stream_screen_topk(const bore_mlp_desc *desc, int n_models, const float *theta,
@@ -1032,49 +1093,13 @@ extern "C" int bore_stream_lbfgsb_minimize(const bore_mlp_desc *desc, int n_mode
   if (D > BORE_DIM_MAX)
     return fail(BORE_E_UNSUPPORTED, "%s: the restarts take D <= BORE_DIM_MAX = %d (got %d)", who, BORE_DIM_MAX, D);
   if (const int rc = lbfgsb_check_args(LbfgsbRequest{desc, n_models, theta, transform, negate, x0, num_starts, lb, ub, opts,
-                                                     x, fun, jac, info}, a.box, a.nbd, a.opt))
+                                                     x, fun, jac, info}, a.r.box, a.r.nbd, a.r.opt))
     return rc;
-  // dynamic LDS beside the static StreamLds: the box, the votes, then per wave the parked State and the optimiser's
-  // fp64 and int workspaces -- every region a multiple of 16 bytes
-  const int De = (D + 1) & ~1;
-  size_t off = 0;
-  a.o_box = 0; off += 4 * (size_t)De + (((size_t)D + 3) & ~(size_t)3);
-  a.o_vote = (int)off; off += 4;
-  a.o_prob = (int)off;
-  const size_t state_f = (sizeof(lbfgsb::State) + 15) / 16 * 4;
-  const size_t dw_f = 2 * (size_t)lbfgsb::dwork_size(D, a.opt.m);
-  const size_t iw_f = ((size_t)lbfgsb::iwork_size(D) + 3) & ~(size_t)3;
-  a.o_dw = (int)state_f;
-  a.o_iw = (int)(state_f + dw_f);
-  a.prob_floats = (int)(state_f + dw_f + iw_f);
-  // (64: the static region's own alignment and the 16 bytes the kernel may skip to align the dynamic one)
-  const size_t room = (size_t)BORE_LDS_BYTES - sizeof(StreamLds) - 64 - off * 4;
-  int waves = (int)(room / ((size_t)a.prob_floats * 4));
-  if (waves > BORE_THREADS / 64) waves = BORE_THREADS / 64;
-  if (waves < 1)
-    return fail(BORE_E_UNSUPPORTED,
-                "%s: one problem's workspace (%zu B at D = %d, maxcor = %d) does not fit the %zu B of LDS beside the "
-                "streamed kernels' panels: lower maxcor", who, (size_t)a.prob_floats * 4, D, a.opt.m, room);
-  a.waves = waves;
-  const size_t lds_bytes = (off + (size_t)waves * a.prob_floats) * 4 + 16;
-  a.theta = theta; a.x0 = x0; a.x = x; a.fun = fun; a.jac = jac; a.info = info;
-  a.R = num_starts; a.transform = transform; a.sign = negate ? -1.f : 1.f;
-  // a model's restarts in groups of `waves`, a workgroup per group -- fewer, each walking several groups, when the
-  // workspaces of all would take more than STREAM_WS_BYTES
-  a.ws_stride = (long long)stream_tile_floats(a.L);
-  const long long groups = ((long long)num_starts + waves - 1) / waves;
-  const long long gy = stream_walkers(n_models, groups, a.ws_stride, false);  // (the restarts take no CU cap)
-  // every round serves one request of every live problem: a wave's problems, one after another, each within the
-  // optimiser's own limit (lbfgsb_round_cap)
-  a.max_rounds = ((groups + gy - 1) / gy) * lbfgsb_round_cap(opts);
-  hipStream_t st = (hipStream_t)stream;
-  if (const int rc = allow_lds(stream_lbfgsb_kernel, lds_bytes)) return rc;
-  HIP_TRY(hipMallocAsync((void **)&a.ws, (size_t)n_models * gy * a.ws_stride * sizeof(float), st));
-  hipLaunchKernelGGL(stream_lbfgsb_kernel, dim3(n_models, (unsigned)gy), dim3(BORE_THREADS), lds_bytes, st, a);
-  const hipError_t e = hipGetLastError();
-  (void)hipFreeAsync(a.ws, st);
-  if (e != hipSuccess) return fail(BORE_E_HIP, "streamed restart kernel: %s", hipGetErrorString(e));
-  return 0;
+  a.theta = theta; a.r.x0 = x0; a.r.x = x; a.r.fun = fun; a.r.jac = jac; a.r.info = info;
+  a.r.R = num_starts; a.r.transform = transform; a.r.sign = negate ? -1.f : 1.f;
+  // (static LDS: the panels; per workgroup one workspace tile)
+  return stream_restart_launch(who, "streamed restart kernel", stream_lbfgsb_kernel, a, D, sizeof(StreamLds), n_models,
+                               (long long)stream_tile_floats(a.L), opts, stream);
 }
 
 extern "C" int bore_stream_svgd_optimize(const bore_mlp_desc *desc, int n_models, const float *theta, int transform,
@@ -1125,12 +1150,10 @@ extern "C" int bore_stream_svgd_optimize(const bore_mlp_desc *desc, int n_models
   a.n = n; a.n_iter = opts->n_iter; a.transform = transform; a.distortion = opts->distortion;
   a.step = opts->step_size; a.alpha = opts->alpha; a.eps = opts->eps; a.tau = opts->tau;
   a.length_scale = opts->length_scale; a.dparam = opts->distortion_param;
-  hipStream_t st = (hipStream_t)stream;
   if (const int rc = allow_lds(stream_svgd_kernel, lds_bytes)) return rc;
-  HIP_TRY(hipMallocAsync((void **)&a.ws, (size_t)n_models * a.ws_stride * sizeof(float), st));
-  hipLaunchKernelGGL(stream_svgd_kernel, dim3(n_models), dim3(BORE_THREADS), lds_bytes, st, a);
-  const hipError_t e = hipGetLastError();
-  (void)hipFreeAsync(a.ws, st);
-  if (e != hipSuccess) return fail(BORE_E_HIP, "streamed SVGD kernel: %s", hipGetErrorString(e));
-  return 0;
+  return with_workspace((size_t)n_models * a.ws_stride, stream, "streamed SVGD kernel", [&](float *ws) {
+    a.ws = ws;
+    hipLaunchKernelGGL(stream_svgd_kernel, dim3(n_models), dim3(BORE_THREADS), lds_bytes, (hipStream_t)stream, a);
+    return 0;
+  });
 }

@@ -89,6 +89,23 @@ inline int launch_lds(K kernel, dim3 grid, dim3 block, size_t lds_bytes, void *s
   return 0;
 }
 
+// A stream-ordered device workspace of `floats` floats around body(ws), which launches on `stream` what uses it and
+// returns the project's rc; behind a body that returns 0 the last HIP error is checked and reported under `what`.
+// The workspace is freed on the stream in every case.
+template <typename Body>
+inline int with_workspace(size_t floats, void *stream, const char *what, Body body) {
+  hipStream_t st = (hipStream_t)stream;
+  float *ws = nullptr;
+  HIP_TRY(hipMallocAsync((void **)&ws, floats * sizeof(float), st));
+  int rc = body(ws);
+  if (rc == 0) {
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) rc = fail(BORE_E_HIP, "%s: %s", what, hipGetErrorString(e));
+  }
+  (void)hipFreeAsync(ws, st);
+  return rc;
+}
+
 // Compute units of the current device (per device, cached).
 inline int device_cus() {
   static int cus[64];

@@ -9,6 +9,7 @@ from scipy.optimize import OptimizeResult
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "native", "lbfgsb_host.cpp")
 HDR = os.path.join(os.path.dirname(HERE), "bore_amd", "csrc", "lbfgsb.h")
+HDR_CARVE = os.path.join(os.path.dirname(HERE), "bore_amd", "csrc", "stream_restart.h")
 SO = os.path.join(HERE, "native", "liblbfgsb_host.so")
 _CB = C.CFUNCTYPE(None, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double))
 _lib = None
@@ -18,7 +19,7 @@ def lib():
     global _lib
     if _lib is None:
         if (not os.path.exists(SO)
-                or os.path.getmtime(SO) < max(os.path.getmtime(SRC), os.path.getmtime(HDR))):
+                or os.path.getmtime(SO) < max(os.path.getmtime(f) for f in (SRC, HDR, HDR_CARVE))):
             subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-ffp-contract=off",
                             SRC, "-o", SO], check=True)
         _lib = C.CDLL(SO)
@@ -43,6 +44,18 @@ def layout(n, m, big_outside=False):
     off, ioff, sizes = (C.c_int * 21)(), (C.c_int * 3)(), (C.c_int * 3)()
     lib().lbfgsb_host_layout(int(n), int(m), int(bool(big_outside)), off, ioff, sizes)
     return (dict(zip(LAYOUT_NAMES, off)), dict(zip(("index", "iwhere", "indx2"), ioff)), sizes[0], sizes[1], sizes[2])
+
+
+CARVE_NAMES = "o_box o_vote o_prob prob_floats o_dw o_iw waves lds_bytes room".split()
+
+
+def stream_restart_carve(D, maxcor, static_bytes, max_waves=4):
+    """stream_restart_carve of bore_amd/csrc/stream_restart.h (the streamed restart kernels' dynamic LDS, float
+    offsets): (fits, {CARVE_NAMES: value}, sizeof(State), dwork_size(D, maxcor), iwork_size(D))."""
+    out, sizes = (C.c_longlong * 9)(), (C.c_int * 3)()
+    fits = lib().lbfgsb_host_stream_restart_carve(int(D), int(maxcor), C.c_longlong(int(static_bytes)), int(max_waves),
+                                                  out, sizes)
+    return bool(fits), dict(zip(CARVE_NAMES, out)), sizes[0], sizes[1], sizes[2]
 
 
 def minimize(fun, x0, bounds, maxcor=10, ftol=2.2204460492503131e-09, gtol=1e-5, maxfun=15000,

@@ -11,10 +11,27 @@ static thread_local int lbfgsb_host_events[32];
 #define LB_EVENT(s_, id) ((void)++lbfgsb_host_events[id])
 
 #include "../../bore_amd/csrc/lbfgsb.h"
+#include "../../bore_amd/csrc/stream_restart.h"
 
 static_assert(lbfgsb::EV_COUNT <= 32, "lbfgsb_host_events is too short");
 
 extern "C" {
+
+// stream_restart_carve, the carve the streamed restart entry points launch with: out = {o_box, o_vote, o_prob,
+// prob_floats, o_dw, o_iw, waves, lds_bytes, room}; sizes = {sizeof(State), dwork_size, iwork_size}.  Returns 1 when a
+// slot fits, else 0.
+int lbfgsb_host_stream_restart_carve(int D, int maxcor, long long static_bytes, int max_waves, long long *out,
+                                     int *sizes) {
+  RestartCarve c;
+  const bool fits = stream_restart_carve(D, maxcor, (size_t)static_bytes, max_waves, &c);
+  const long long v[9] = {c.lds.o_box, c.lds.o_vote, c.lds.o_prob, c.lds.prob_floats, c.lds.o_dw,
+                          c.lds.o_iw,  c.waves,      (long long)c.lds_bytes, (long long)c.room};
+  for (int i = 0; i < 9; ++i) out[i] = v[i];
+  sizes[0] = (int)sizeof(lbfgsb::State);
+  sizes[1] = lbfgsb::dwork_size(D, maxcor);
+  sizes[2] = lbfgsb::iwork_size(D);
+  return fits ? 1 : 0;
+}
 
 typedef void (*fg_callback)(int n, const double *x, double *f, double *g);
 
