@@ -18,7 +18,7 @@ CSRC = os.path.join(_HERE, "csrc")
 # only ever LOADED: build_native() writes the default path and nothing else.)
 DEFAULT_LIB_PATH = os.path.join(CSRC, "libbore_hip.so")
 LIB_PATH = os.environ.get("BORE_LIB_PATH") or DEFAULT_LIB_PATH
-SOURCES = ["bore_all.hip"]   # a unity build of bore_{hip,argmax,svgd,iter,engine,lstm,stream,lstm_stream}.hip
+SOURCES = ["bore_all.hip"]   # a unity build of bore_{hip,argmax,svgd,iter,engine,lstm,stream,lstm_stream,ensemble}.hip
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "bore_hip.h")
 
 # The replica engine runs up to a dozen independent launches on as many HIP streams; ROCm gives a
@@ -30,6 +30,7 @@ MAX_LAYERS = 8
 BATCH_MAX = 64
 STREAM_MAX_UNITS = 512   # include/bore_hip.h BORE_STREAM_MAX_UNITS
 STREAM_MAX_SAMPLES = 16384   # include/bore_hip.h BORE_STREAM_MAX_SAMPLES
+ENSEMBLE_MAX_MEMBERS = 16    # include/bore_hip.h BORE_ENSEMBLE_MAX_MEMBERS
 
 ACT = dict(linear=0, relu=1, elu=2, sigmoid=3, tanh=4)
 TRANSFORM = dict(identity=0, sigmoid=1, exp=2)
@@ -59,6 +60,8 @@ EXPORTS = [
     "bore_lstm_stream_fit", "bore_lstm_stream_evaluate", "bore_lstm_streamed", "bore_mlp_streamed",
     "bore_stream_screen_topk", "bore_stream_sample_screen_topk", "bore_stream_lbfgsb_minimize",
     "bore_stream_svgd_optimize", "bore_lstm_stream_screen_topk", "bore_lstm_stream_lbfgsb_minimize",
+    "bore_ensemble_value_and_input_grad", "bore_ensemble_screen_topk", "bore_ensemble_lbfgsb_minimize",
+    "bore_ensemble_plan_query",
 ]
 
 
@@ -277,6 +280,12 @@ def lib():
     L.bore_lstm_stream_screen_topk.argtypes = [lp, i32, vp, vp, i64, i32, i32, i32, vp, vp, vp, vp]
     L.bore_lstm_stream_lbfgsb_minimize.argtypes = [lp, i32, vp, i32, i32, i32, vp, i32, dpp, dpp,
                                                    C.POINTER(LbfgsbOpts), vp, vp, vp, vp, vp]
+    f64 = C.c_double
+    L.bore_ensemble_value_and_input_grad.argtypes = [dp, i32, i32, vp, vp, i64, f64, i32, i32, vp, vp, vp]
+    L.bore_ensemble_screen_topk.argtypes = [dp, i32, i32, vp, vp, i64, i32, f64, i32, vp, vp, vp, vp]
+    L.bore_ensemble_lbfgsb_minimize.argtypes = [dp, i32, i32, vp, f64, i32, i32, vp, i32, dpp, dpp,
+                                                C.POINTER(LbfgsbOpts), vp, vp, vp, vp, vp]
+    L.bore_ensemble_plan_query.argtypes = [dp, i32, i32, f64, i32, i32, C.POINTER(C.c_int32), i32]
     for name in EXPORTS:
         if name not in ("bore_last_error", "bore_param_count", "bore_lstm_param_count", "bore_engine_size",
                         "bore_engine_destroy", "bore_set_batch"):

@@ -9,3 +9,4 @@
 #include "bore_lstm.hip"
 #include "bore_stream.hip"
 #include "bore_lstm_stream.hip"
+#include "bore_ensemble.hip"

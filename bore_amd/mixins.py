@@ -86,7 +86,12 @@ class MaximizableMixin:
         bore/mixins.py:45-52)."""
         (low, high), dim = from_bounds(bounds)
         X_init = random_state.uniform(low=low, high=high, size=(num_samples, dim))
-        return X_init, -self.predict(X_init).squeeze(axis=-1)
+        return X_init, self._screen_values(X_init)
+
+    def _screen_values(self, X_init):
+        """What the host screening ranks the candidates by, ascending: the negated ``predict`` (a model that scores by
+        something else -- an ensemble -- overrides this)."""
+        return -self.predict(X_init).squeeze(axis=-1)
 
     def _minimize_on_device(self, X0, bounds, options):
         import torch
@@ -237,7 +242,7 @@ class MaximizableMixin:
                 f_init = None                          # (the literal form below says why, or takes another route)
                 self._screening_refused(e)
         if f_init is None:
-            f_init = -self.predict(X_init).squeeze(axis=-1)
+            f_init = self._screen_values(X_init)
 
         if num_starts == 0:
             # legal: the best random sample, wrapped (bore/mixins.py:67-70)

@@ -113,6 +113,18 @@ class Sequential:
                                     [l.l2_bias for l in self.layers],
                                     compute="bfloat16" if self.dtype_policy == "mixed_bfloat16"
                                     else "float32")
+        P = ops.param_count(self._desc)
+        flat = np.stack([self._draw_initial() for _ in range(self._n_models)])     # (one model; an ensemble: its members)
+        assert flat.shape == (self._n_models, P)
+        self.theta = torch.from_numpy(flat).to(dev).contiguous()
+        self.adam_m = torch.zeros_like(self.theta)
+        self.adam_v = torch.zeros_like(self.theta)
+        self.adam_t = torch.zeros(self._n_models, dtype=torch.int64, device=dev)
+
+    _n_models = 1      # rows of theta
+
+    def _draw_initial(self):
+        """One model's packed initial parameters from the model's stream: glorot_uniform kernels, zero biases."""
         ws = []
         fan_in = self._input_dim
         for l in self.layers:
@@ -120,13 +132,7 @@ class Sequential:
             ws.append(self._rs.uniform(-limit, limit, size=(fan_in, l.units)).astype(np.float32))
             ws.append(np.zeros(l.units, dtype=np.float32))
             fan_in = l.units
-        flat = np.concatenate([w.reshape(-1) for w in ws])
-        P = ops.param_count(self._desc)
-        assert flat.size == P
-        self.theta = torch.from_numpy(flat).to(dev).reshape(1, P).contiguous()
-        self.adam_m = torch.zeros_like(self.theta)
-        self.adam_v = torch.zeros_like(self.theta)
-        self.adam_t = torch.zeros(1, dtype=torch.int64, device=dev)
+        return np.concatenate([w.reshape(-1) for w in ws])
 
     def _ensure_built(self, x):
         if not self.built:
@@ -236,6 +242,12 @@ class Sequential:
                              else y.reshape(-1), torch.float32).reshape(1, N)
             w = resolve_sample_weight(N, y, sample_weight, class_weight)
             W = None if w is None else torch.from_numpy(w).to(self.theta.device).reshape(1, N)
+        return self._run_fit(X, z, W, N, epochs, batch_size, perm, shuffle, verbose, callbacks)
+
+    def _run_fit(self, X, z, W, N, epochs, batch_size, perm, shuffle, verbose, callbacks, n_models=1):
+        """The launches of ``fit`` behind the upload: X [L, N, D], z [L, N], W [L, N] or None on the device for the
+        L = ``n_models`` models of ``theta`` (1: this model; an ensemble: its members, which share ``perm``).  The
+        logged loss is the mean over the models."""
         epochs = int(epochs)
         if perm is None and not shuffle:
             perm = np.tile(np.arange(N, dtype=np.int32), (epochs, 1))
@@ -246,7 +258,10 @@ class Sequential:
                 raise ValueError("perm must hold one permutation of range(N) per epoch")
             perm = torch.from_numpy(np.ascontiguousarray(perm, dtype=np.int32)) \
                 .to(self.theta.device).reshape(1, epochs, N)
+            if n_models > 1:
+                perm = perm.expand(n_models, epochs, N).contiguous()
         o = self._optimizer
+        logged = (lambda loss: loss[0]) if n_models == 1 else (lambda loss: loss.mean(dim=0))
 
         def launch(e0, n_epochs):
             kw = dict(seed=self._shuffle_seed, epoch0=self._epochs_seen, lr=o.learning_rate,
@@ -261,25 +276,25 @@ class Sequential:
                 # A data set too long for the device to draw its shuffles in LDS (the reference's fit
                 # takes whatever the record holds, README.rst:93): the SAME stream from its host
                 # statement (bore_amd.shuffle), a few epochs per launch, read from memory by the kernel.
-                chunk = max(1, min(n_epochs, (64 << 20) // (4 * N)))
+                chunk = max(1, min(n_epochs, (64 << 20) // (4 * N * n_models)))
                 parts = []
                 for c0 in range(0, n_epochs, chunk):
                     ne = min(chunk, n_epochs - c0)
-                    pc = _shuffle.permutations(self._shuffle_seed, 1, ne, N, epoch0=self._epochs_seen + c0)
+                    pc = _shuffle.permutations(self._shuffle_seed, n_models, ne, N, epoch0=self._epochs_seen + c0)
                     pc = torch.from_numpy(pc).to(self.theta.device)
                     parts.append(ops.mlp_fit(self._desc, self.theta, self.adam_m, self.adam_v, self.adam_t,
                                              X, z, ne, batch_size, perm=pc, **kw))
                 loss = torch.cat(parts, dim=1)
             self._epochs_seen += n_epochs
-            return loss
+            return logged(loss)
 
         callbacks = list(callbacks or [])
         if not callbacks:
             loss = launch(0, epochs)                 # (enqueued: nothing waits for the kernel here)
             if verbose:
-                for e, v in enumerate(loss[0].cpu().numpy()):
+                for e, v in enumerate(loss.cpu().numpy()):
                     print(f"Epoch {e + 1}/{epochs} - loss: {float(v):.4f}")
-            return History(lambda: loss[0].cpu().numpy())
+            return History(lambda: loss.cpu().numpy())
 
         def call(name, *args):
             for cb in callbacks:
@@ -293,7 +308,7 @@ class Sequential:
         losses = []
         for e in range(epochs):
             call("on_epoch_begin", e, {})
-            losses.append(float(launch(e, 1)[0].cpu().numpy()[0]))
+            losses.append(float(launch(e, 1).cpu().numpy()[0]))
             call("on_epoch_end", e, {"loss": losses[-1]})
             if self.stop_training:
                 break
@@ -330,7 +345,10 @@ class Sequential:
         """Keras order [W1 (in,out), b1, W2, b2, ...] as float32 numpy arrays."""
         if not self.built:
             raise RuntimeError("model is not built yet")
-        flat = self.theta[0].cpu().numpy()
+        return self._unpack(self.theta[0].cpu().numpy())
+
+    def _unpack(self, flat):
+        """A packed parameter vector as the Keras-order list."""
         out, off, fan_in = [], 0, self._input_dim
         for l in self.layers:
             out.append(flat[off:off + fan_in * l.units].reshape(fan_in, l.units).copy())
@@ -421,6 +439,194 @@ class BatchMaximizableSequential(BatchMaximizableMixin, Sequential):
 
 class BatchMaximizableDenseSequential(BatchMaximizableMixin, DenseSequential):
     pass
+
+
+class EnsembleSequential(Sequential):
+    """``members`` classifiers of one Dense stack, fitted together and read together (an extension over the reference;
+    ``bore_amd.ensemble`` states the semantics).  ``theta``, ``adam_m``, ``adam_v`` are ``[K, P]`` and ``adam_t`` is
+    ``[K]``: member k draws its own glorot initialisation from the model's seeded stream (member 0 first) and shuffles
+    by its own stream (``model_index0 + k``).  ``fit`` is ONE ``ops.mlp_fit`` launch with ``n_models = K`` -- a
+    workgroup per member, up to the device's compute units in about the time of one -- so member k's parameters, Adam
+    slots and counter equal a lone model's fitted from that member's initial weights with the same seed and
+    ``model_index0 = k``, bit for bit.  ``predict`` is the members' mean.
+
+    Refused by name (``UnsupportedError``): ``dtype_policy="mixed_bfloat16"`` and, at build, a network only the
+    streamed kernels take (``ops.mlp_streamed(desc) & 2``)."""
+
+    def __init__(self, layers=None, members=4, beta=1.0, **kwargs):
+        from .ensemble import check_beta, check_members
+        self.members = check_members(members)
+        self.beta = check_beta(beta)
+        if kwargs.get("dtype_policy", "float32") == "mixed_bfloat16":
+            raise _lib.UnsupportedError("an ensemble's members are float32 networks: dtype_policy='mixed_bfloat16' is "
+                                        "not available")
+        super(EnsembleSequential, self).__init__(layers, **kwargs)
+
+    @property
+    def _n_models(self):
+        return self.members
+
+    def build(self, input_dim=None):
+        if self.built:
+            return
+        super(EnsembleSequential, self).build(input_dim)
+        if ops.mlp_streamed(self._desc) & 2:
+            self.theta = self.adam_m = self.adam_v = self.adam_t = None
+            raise _lib.UnsupportedError("this network does not fit one workgroup's LDS (only the streamed kernels take "
+                                        "it): ensembles keep every member's parameters in LDS")
+
+    def _replicated(self, t):
+        """[1, ...] -> [K, ...] on the device: every member sees the same rows."""
+        return t.expand(self.members, *t.shape[1:]).contiguous()
+
+    def fit(self, x, y, batch_size=None, epochs=1, verbose=False, callbacks=None, shuffle=True,
+            perm=None, sample_weight=None, class_weight=None, **kwargs):
+        """``Sequential.fit`` for all members in one launch per call (per epoch with callbacks): the data replicated on
+        the device, ``sample_weight`` / ``class_weight`` and ``perm`` -- (epochs, N), shared by the members -- as
+        there; the logged loss is the mean over the members."""
+        x = np.asarray(x) if not isinstance(x, torch.Tensor) else x
+        self._ensure_built(x)
+        self._check_loss()
+        batch_size = 32 if batch_size is None else int(batch_size)
+        if batch_size < 1:
+            raise ValueError(f"batch_size must be positive, got {batch_size}")
+        X1 = self._to_dev(x, torch.float32).reshape(1, -1, self._input_dim)
+        N = X1.shape[1]
+        yv = y.reshape(-1) if isinstance(y, torch.Tensor) else np.asarray(y).reshape(-1)
+        w = resolve_sample_weight(N, y, sample_weight, class_weight)
+        X = self._replicated(X1)
+        z = self._replicated(self._to_dev(yv, torch.float32).reshape(1, N))
+        W = None if w is None else self._replicated(torch.from_numpy(w).to(self.theta.device).reshape(1, N))
+        return self._run_fit(X, z, W, N, epochs, batch_size, perm, shuffle, verbose, callbacks, n_models=self.members)
+
+    def predict_members(self, x):
+        """(N, D) -> (K, N, 1) float32: every member's ``predict``."""
+        self._ensure_built(x)
+        X = self._to_dev(x, torch.float32).reshape(-1, self._input_dim)
+        return ops.mlp_forward(self._desc, self.theta, X).cpu().numpy()[..., None]
+
+    def _stats(self, x, beta):
+        from .ensemble import ensemble_stats
+        return ensemble_stats(self.predict_members(x)[..., 0], beta)
+
+    def predict(self, x, batch_size=None, verbose=0, **kwargs):
+        """The members' mean mu: (N, D) -> (N, 1) float32."""
+        return self._stats(x, 0.0)[0].astype(np.float32).reshape(-1, 1)
+
+    def predict_std(self, x):
+        """The members' spread sigma = sqrt(var + 1e-12): (N, D) -> (N, 1) float32."""
+        return self._stats(x, 0.0)[1].astype(np.float32).reshape(-1, 1)
+
+    def predict_score(self, x):
+        """The acquisition's score s = mu + beta sigma: (N, D) -> (N, 1) float32."""
+        return self._stats(x, self.beta)[2].astype(np.float32).reshape(-1, 1)
+
+    def evaluate(self, x, y, batch_size=None, verbose=False, sample_weight=None, **kwargs):
+        """[mean member loss, accuracy of mu] (the loss alone without metrics).  The accuracy compares mu with 0.5, as
+        the evaluate kernel compares a member's output (Keras' binary_accuracy), whatever the head."""
+        self._ensure_built(x)
+        self._check_loss()
+        X1 = self._to_dev(x, torch.float32).reshape(1, -1, self._input_dim)
+        zv = np.asarray(y).reshape(-1)
+        z1 = self._to_dev(zv, torch.float32).reshape(1, X1.shape[1])
+        w = resolve_sample_weight(X1.shape[1], None, sample_weight, None)
+        W = None if w is None else self._replicated(torch.from_numpy(w).to(self.theta.device).reshape(1, -1))
+        loss, _ = ops.mlp_evaluate(self._desc, self.theta, self._replicated(X1), self._replicated(z1), sample_weight=W)
+        mean_loss = float(loss.mean())
+        if not self._metrics:
+            return mean_loss
+        mu = self.predict(x)[:, 0]
+        return [mean_loss, float(np.mean((mu > 0.5) == (zv.astype(np.float32) > 0.5)))]
+
+    def _member(self, member):
+        if isinstance(member, bool) or int(member) != member or not 0 <= int(member) < self.members:
+            raise ValueError(f"member must be in 0..{self.members - 1}, got {member!r}")
+        return int(member)
+
+    def get_weights(self, member=0):
+        """Keras-order weights of one member."""
+        k = self._member(member)
+        if not self.built:
+            raise RuntimeError("model is not built yet")
+        return self._unpack(self.theta[k].cpu().numpy())
+
+    def set_weights(self, weights, member=0):
+        k = self._member(member)
+        if not self.built:
+            self.build(np.shape(weights[0])[0])
+        cur = self.get_weights(k)
+        if len(weights) != len(cur) or any(np.shape(a) != b.shape for a, b in zip(weights, cur)):
+            raise ValueError("weight shapes do not match the model")
+        flat = np.concatenate([np.asarray(w, dtype=np.float32).reshape(-1) for w in weights])
+        self.theta[k].copy_(torch.from_numpy(flat))
+
+    def get_optimizer_state(self, member=0):
+        k = self._member(member)
+        return (self.adam_m[k].cpu().numpy(), self.adam_v[k].cpu().numpy(), int(self.adam_t[k]))
+
+    def set_optimizer_state(self, m, v, t, member=0):
+        k = self._member(member)
+        self.adam_m[k].copy_(torch.from_numpy(np.asarray(m, dtype=np.float32)).reshape(-1))
+        self.adam_v[k].copy_(torch.from_numpy(np.asarray(v, dtype=np.float32)).reshape(-1))
+        self.adam_t[k] = int(t)
+
+
+class EnsembleDenseSequential(EnsembleSequential):
+    """``DenseSequential``'s stack (its ``num_layers + 1`` hidden layers included) as an ensemble."""
+
+    def __init__(self, input_dim, output_dim, num_layers, num_units, layer_kws={}, final_layer_kws={}, **kwargs):
+        super(EnsembleDenseSequential, self).__init__(**kwargs)
+        for i in range(num_layers):
+            if not i:
+                self.add(Dense(num_units, input_dim=input_dim, **layer_kws))
+            self.add(Dense(num_units, **layer_kws))
+        self.add(Dense(output_dim, **final_layer_kws))
+        if self._input_dim is None:       # num_layers == 0
+            self._input_dim = int(input_dim)
+
+
+class _MaximizableEnsembleMixin(MaximizableMixin):
+    """``maxima`` / ``argmax`` over an ensemble: the objective is T(-s), s = mu + beta sigma.  The device route runs the
+    ensemble kernels (``ops.ensemble_screen_topk``, ``ops.ensemble_lbfgsb_minimize``); ``restart_mode="lockstep"`` /
+    ``"sequential"``, other SciPy methods, ``num_starts=0`` and callable transforms run on the host through
+    ``ensemble.ensemble_score``, the members' f and g from ONE ``ops.mlp_value_and_input_grad`` launch with
+    ``n_models = K``.  What the ensemble kernels refuse (K images too large for LDS, more than 64 inputs) takes that
+    lock-step route with a ``RuntimeWarning``."""
+
+    def _device_ops(self):
+        beta = self.beta
+
+        def screen(desc, theta, X_init, num_starts, want_pred=False):
+            return ops.ensemble_screen_topk(desc, theta[None], X_init, num_starts, beta, want_score=want_pred)
+
+        def restarts(desc, theta, x0, low, high, transform="identity", negate=True, **options):
+            return ops.ensemble_lbfgsb_minimize(desc, theta[None], x0, low, high, beta, transform, negate, **options)
+
+        return screen, restarts
+
+    def _streamed(self, x=None):
+        return False          # (refused at build)
+
+    def _screen_values(self, X_init):
+        """The NEGATED score -s of the candidates on the host (no transform: T is monotone)."""
+        return -self.predict_score(X_init).squeeze(axis=-1)
+
+    def _value_and_input_grad(self, X, transform, negate):
+        """The hook base.convert takes: X [1, R, D] f64 device -> (val [1, R] f32, grad [1, R, D] f64), the host
+        statement over the members' f and g."""
+        from .ensemble import ensemble_score
+        f, g = ops.mlp_value_and_input_grad(self._desc, self.theta, self._replicated(X), "identity", False)
+        val, grad = ensemble_score(f.cpu().numpy(), g.cpu().numpy(), self.beta, transform, negate)
+        return torch.from_numpy(val.astype(np.float32)[None]), torch.from_numpy(np.ascontiguousarray(grad)[None])
+
+
+class MaximizableEnsembleSequential(_MaximizableEnsembleMixin, EnsembleSequential):
+    """``MaximizableSequential(transform, ...)`` over ``members`` classifiers: ``MaximizableEnsembleSequential(transform,
+    members=K, beta=1.0, seed=...)``."""
+
+
+class MaximizableEnsembleDenseSequential(_MaximizableEnsembleMixin, EnsembleDenseSequential):
+    """``MaximizableDenseSequential``'s constructor arguments plus ``members`` and ``beta``."""
 
 
 class LSTMCell:
@@ -814,6 +1020,7 @@ class MaximizableOneToOneNetwork(MaximizableMixin, OneToOneNetwork):
 
 __all__ = ["Sequential", "DenseSequential", "Model", "MaximizableModel", "MaximizableSequential",
            "MaximizableDenseSequential", "BatchMaximizableModel", "BatchMaximizableSequential",
-           "BatchMaximizableDenseSequential", "Dense", "BinaryCrossentropy", "Adam", "History",
+           "BatchMaximizableDenseSequential", "EnsembleSequential", "EnsembleDenseSequential",
+           "MaximizableEnsembleSequential", "MaximizableEnsembleDenseSequential", "Dense", "BinaryCrossentropy", "Adam", "History",
            "LSTMCell", "StackedRecurrentFactory", "ManyToManyNetwork", "OneToOneNetwork",
            "MaximizableOneToOneNetwork"]

@@ -677,3 +677,82 @@ def lstm_stream_lbfgsb_minimize(desc, theta, x0, low, high, num_steps, transform
     ``lstm_stream_value_and_input_grad``'s f and g, bit for bit."""
     return _lbfgsb_minimize(_lib.lib().bore_lstm_stream_lbfgsb_minimize, desc, theta, x0, low, high, transform, negate,
                             count=lstm_param_count, steps=(int(num_steps),), **options)
+
+
+# ------------------------------------------------------------------------------------------------
+# classifier ensembles (include/bore_hip.h bore_ensemble_*): theta [E, K, P], K members per ensemble
+# ------------------------------------------------------------------------------------------------
+ENSEMBLE_PLAN_FIELDS = ("K", "P_lds", "image_bytes", "pass_bytes", "lds_bytes", "waves", "slot_bytes", "ens_base",
+                        "o_layout", "o_pre", "o_theta", "o_x", "o_wave", "wave_floats", "o_f", "o_g", "o_val", "o_grad",
+                        "total", "o_box", "o_vote", "o_prob", "o_dw", "o_iw")   # BORE_ENSEMBLE_PLAN_FIELDS
+
+
+def ensemble_plan_query(desc, n_ens, members, beta=0.0, maxcor=0, batch_mode=False):
+    """What the ensemble kernels would launch for these sizes (``bore_ensemble_plan_query``): a dict of
+    ``ENSEMBLE_PLAN_FIELDS`` -- the LDS bytes of the K images and of the pass, the launch's dynamic LDS, the waves that
+    hold a restart problem, the carve.  ``maxcor`` 0: the value + gradient / screening launch; 1..32: the restarts'.
+    A host query (no GPU, nothing launched); a refusal raises with the bound named."""
+    out = (C.c_int32 * len(ENSEMBLE_PLAN_FIELDS))()
+    _lib.check(_lib.lib().bore_ensemble_plan_query(C.byref(desc), int(n_ens), int(members), float(beta), int(maxcor),
+                                                   int(bool(batch_mode)), out, len(ENSEMBLE_PLAN_FIELDS)))
+    return dict(zip(ENSEMBLE_PLAN_FIELDS, out))
+
+
+def _chk_ensemble_theta(desc, theta):
+    if not isinstance(theta, torch.Tensor) or theta.dim() != 3:
+        raise ValueError("theta: expected [n_ensembles, members, P]")
+    E, K, _ = theta.shape
+    _chk(theta, torch.float32, (E, K, param_count(desc)), "theta")
+    return E, K
+
+
+def ensemble_value_and_input_grad(desc, theta, X, beta=0.0, transform="identity", negate=True):
+    """theta [E,K,P] f32; X [E,R,D] f64 -> (val [E,R] f32, grad [E,R,D] f64) of T(+-s), s = mu + beta sigma over the K
+    members (``bore_amd.ensemble.ensemble_score`` is the statement)."""
+    E, K = _chk_ensemble_theta(desc, theta)
+    D = desc.input_dim
+    if X.dim() != 3:
+        raise ValueError("X: expected [n_ensembles, n_rows, D]")
+    R = X.shape[1]
+    _chk(X, torch.float64, (E, R, D), "X")
+    if transform not in _lib.TRANSFORM:
+        raise ValueError(f"unknown transform {transform!r}")
+    val = torch.empty((E, R), dtype=torch.float32, device=theta.device)
+    grad = torch.empty((E, R, D), dtype=torch.float64, device=theta.device)
+    _lib.check(_lib.lib().bore_ensemble_value_and_input_grad(
+        C.byref(desc), E, K, _lib.ptr(theta), _lib.ptr(X), R, float(beta), _lib.TRANSFORM[transform],
+        int(bool(negate)), _lib.ptr(val), _lib.ptr(grad), _lib.stream_ptr()))
+    return val, grad
+
+
+def ensemble_screen_topk(desc, theta, X_init, num_starts, beta=0.0, want_score=False):
+    """Screening over an ensemble: s = mu + beta sigma of the candidates X_init ([E,Ns,D] or shared [Ns,D], f64) and
+    the R = num_starts best rows (descending s, ties to the lower row): (x0 [E,R,D] f64, idx [E,R] int32[, score
+    [E,Ns] f32])."""
+    E, K = _chk_ensemble_theta(desc, theta)
+    D = desc.input_dim
+    shared = X_init.dim() == 2
+    Ns = X_init.shape[-2]
+    _chk(X_init, torch.float64, (Ns, D) if shared else (E, Ns, D), "X_init")
+    R = int(num_starts)
+    x0 = torch.empty((E, R, D), dtype=torch.float64, device=theta.device)
+    idx = torch.empty((E, R), dtype=torch.int32, device=theta.device)
+    score = torch.empty((E, Ns), dtype=torch.float32, device=theta.device) if want_score else None
+    _lib.check(_lib.lib().bore_ensemble_screen_topk(
+        C.byref(desc), E, K, _lib.ptr(theta), _lib.ptr(X_init), Ns, int(shared), float(beta), R, _lib.ptr(x0),
+        _lib.ptr(idx), _lib.ptr(score), _lib.stream_ptr()))
+    return (x0, idx, score) if want_score else (x0, idx)
+
+
+def ensemble_lbfgsb_minimize(desc, theta, x0, low, high, beta=0.0, transform="identity", negate=True, **options):
+    """``lbfgsb_minimize`` of T(+-s) over an ensemble (``bore_ensemble_lbfgsb_minimize``, D <= 64): theta [E,K,P], x0
+    [E,R,D] f64.  The same packed results (``lbfgsb_results_to_host``: one copy); every record is the host build of
+    the optimiser fed ``ensemble_value_and_input_grad``'s f and g, bit for bit."""
+    E, K = _chk_ensemble_theta(desc, theta)
+    entry = _lib.lib().bore_ensemble_lbfgsb_minimize
+
+    def call(desc_ref, n_ens, theta_p, *rest):
+        return entry(desc_ref, n_ens, K, theta_p, float(beta), *rest)
+
+    return _lbfgsb_minimize(call, desc, theta.view(E, -1), x0, low, high, transform, negate,
+                            count=lambda d: K * param_count(d), **options)

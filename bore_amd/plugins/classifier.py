@@ -22,7 +22,7 @@ from ..base import maybe_distort
 from ..data import LFBO_WEIGHTINGS, Record
 from ..layers import BinaryCrossentropy, l2
 from ..math import steps_per_epoch
-from ..models import MaximizableDenseSequential
+from ..models import MaximizableDenseSequential, MaximizableEnsembleDenseSequential
 from ..optimizers.utils import from_bounds
 from ..transforms import TRANSFORMS
 
@@ -33,13 +33,21 @@ class ClassifierSuggester:
                  num_epochs_per_iter=None, optimizer="adam", num_layers=2, num_units=32,
                  activation="elu", l2_factor=None, transform="sigmoid", method="L-BFGS-B",
                  max_iter=1000, ftol=1e-9, distortion=None, seed=None, logger=None, space=None,
-                 weighting=None, normalize_utility=True):
+                 weighting=None, normalize_utility=True, ensemble=None, beta=1.0):
         """space: a ``DenseSpace``; then ``bounds`` is its unit box, ``suggest()`` returns a
         configuration dictionary and ``observe()`` takes one.
 
         weighting: None (BORE, the reference), or "ei" / "lfbo": the classifier of likelihood-free BO -- every update
         fits on ``Record.load_lfbo_data``'s targets and row weights (``bore_amd.data.lfbo_targets``;
-        ``normalize_utility``: the improvement divided by its mean over the positives)."""
+        ``normalize_utility``: the improvement divided by its mean over the positives).
+
+        ensemble: None (one classifier: the reference, today's code path), or K = 1..16: K classifiers fitted in one
+        launch, the acquisition their upper confidence bound mean + ``beta`` x spread (``bore_amd.ensemble``,
+        ``MaximizableEnsembleDenseSequential``).  Composes with ``weighting``: that is only a weighted fit."""
+        if ensemble is not None:
+            from ..ensemble import check_beta, check_members
+            ensemble, beta = check_members(ensemble), check_beta(beta)
+        self.ensemble, self.beta = ensemble, beta
         if weighting is not None and weighting not in LFBO_WEIGHTINGS:
             raise ValueError(f"weighting must be None or one of {LFBO_WEIGHTINGS} (got {weighting!r})")
         self.weighting, self.normalize_utility = weighting, bool(normalize_utility)
@@ -84,12 +92,15 @@ class ClassifierSuggester:
         # (the reference leaves weight init and shuffling to TF's global seed; here a seeded
         # suggester is reproducible end to end: every network it builds draws from one stream)
         net_seed = None if self.seed is None else int(self._net_rng.randint(0, 2**31 - 1))
-        network = MaximizableDenseSequential(
+        cls, extra = MaximizableDenseSequential, {}
+        if self.ensemble is not None:
+            cls, extra = MaximizableEnsembleDenseSequential, dict(members=self.ensemble, beta=self.beta)
+        network = cls(
             transform=self.transform, input_dim=self.input_dim, output_dim=1,
             num_layers=self.num_layers, num_units=self.num_units,
             layer_kws=dict(activation=self.activation,
                            kernel_regularizer=self.kernel_regularizer,
-                           bias_regularizer=self.bias_regularizer), seed=net_seed)
+                           bias_regularizer=self.bias_regularizer), seed=net_seed, **extra)
         network.compile(optimizer=self.optimizer, metrics=["accuracy"],
                         loss=BinaryCrossentropy(from_logits=True))
         network.summary(print_fn=self.logger.debug)

@@ -74,7 +74,8 @@ class ClassifierConfigGenerator(_GeneratorBase):
             method=optimizer_kws.get("method", "L-BFGS-B"),
             ftol=optimizer_kws.get("ftol", 1e-9), max_iter=optimizer_kws.get("max_iter", 1000),
             distortion=optimizer_kws.get("distortion"), seed=seed, logger=self.logger,
-            weighting=fit_kws.get("weighting"), normalize_utility=fit_kws.get("normalize_utility", True))
+            weighting=fit_kws.get("weighting"), normalize_utility=fit_kws.get("normalize_utility", True),
+            ensemble=classifier_kws.get("ensemble"), beta=classifier_kws.get("beta", 1.0))
         s = self._suggester
         self.gamma, self.num_random_init, self.random_rate = s.gamma, s.num_random_init, s.random_rate
         self.input_dim, self.bounds = s.input_dim, s.bounds
@@ -107,15 +108,16 @@ class BORE(_HyperBand):
                  batch_size=64, num_steps_per_iter=1000, num_epochs_per_iter=None, optimizer="adam",
                  num_layers=2, num_units=32, activation="elu", l2_factor=None, transform="sigmoid",
                  method="L-BFGS-B", max_iter=1000, ftol=1e-9, distortion=None, seed=None, weighting=None,
-                 normalize_utility=True, **kwargs):
-        """weighting, normalize_utility: ``ClassifierSuggester``'s (None: BORE; "ei" / "lfbo": likelihood-free BO)."""
+                 normalize_utility=True, ensemble=None, beta=1.0, **kwargs):
+        """weighting, normalize_utility: ``ClassifierSuggester``'s (None: BORE; "ei" / "lfbo": likelihood-free BO);
+        ensemble, beta: its too (None: one classifier; K: an ensemble of K, acquisition mean + beta x spread)."""
         if gamma is None:
             gamma = 1 / eta
         cg = ClassifierConfigGenerator(
             config_space=config_space, gamma=gamma, num_random_init=num_random_init,
             random_rate=random_rate, retrain=retrain,
             classifier_kws=dict(num_layers=num_layers, num_units=num_units, l2_factor=l2_factor,
-                                activation=activation, optimizer=optimizer),
+                                activation=activation, optimizer=optimizer, ensemble=ensemble, beta=beta),
             fit_kws=dict(batch_size=batch_size, num_steps_per_iter=num_steps_per_iter,
                          num_epochs_per_iter=num_epochs_per_iter, weighting=weighting,
                          normalize_utility=normalize_utility),
@@ -151,6 +153,13 @@ def _refuse_weighting(weighting):
                                "(BORE / ClassifierSuggester take a weighting)")
 
 
+def _refuse_ensemble(ensemble):
+    if ensemble is not None:
+        from .._lib import UnsupportedError
+        raise UnsupportedError(f"ensemble={ensemble!r}: the ensemble kernels take Dense members, not the recurrent "
+                               "classifier (BORE / ClassifierSuggester take an ensemble)")
+
+
 class SequenceClassifierConfigGenerator(_GeneratorBase):
     """:95-329.  An LSTM classifier (``StackedRecurrentFactory``) over the rungs of the ladder: the
     many-to-many network is fitted on the label sequences of every configuration, and a one-to-one
@@ -161,6 +170,7 @@ class SequenceClassifierConfigGenerator(_GeneratorBase):
                  fit_kws, optimizer_kws, seed, **kwargs):
         super().__init__(**kwargs)
         _refuse_weighting(fit_kws.get("weighting"))
+        _refuse_ensemble(classifier_kws.get("ensemble"))
         from ..data import MultiFidelityRecord
         from ..layers import l2
         from ..models import StackedRecurrentFactory
@@ -294,9 +304,11 @@ class BOREHyperband(_HyperBand):
                  num_steps_per_iter=1000, num_epochs=None, optimizer="adam", mask_value=-1., num_layers=2,
                  num_units=32, activation="elu", l2_factor=None, transform="sigmoid", method="L-BFGS-B",
                  max_iter=1000, ftol=1e-9, distortion=None, seed=None, acquisition="lockstep", weighting=None,
-                 **kwargs):
-        """weighting: anything but None raises ``UnsupportedError`` (the recurrent fits take no sample weights)."""
+                 ensemble=None, **kwargs):
+        """weighting: anything but None raises ``UnsupportedError`` (the recurrent fits take no sample weights);
+        ensemble: likewise (the ensemble kernels take Dense members)."""
         _refuse_weighting(weighting)
+        _refuse_ensemble(ensemble)
         if gamma is None:
             gamma = 1 / eta
         cg = SequenceClassifierConfigGenerator(

@@ -831,6 +831,57 @@ int bore_lstm_stream_lbfgsb_minimize(const bore_lstm_desc *desc, int n_models, c
                                      const double *lb, const double *ub, const bore_lbfgsb_opts *opts,
                                      double *x, double *fun, double *jac, int32_t *info, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Classifier ENSEMBLES (bore_ensemble.hip): K members of one bore_mlp_desc, theta [n_ens][K][P], and an acquisition
+ * that reads all of them.  An extension over the reference; opt-in; additive to ABI 12.  f_k(x): member k's network
+ * output in float32 (bore_mlp_forward's value: a logit or a probability, as the net is built).  Combined in float64
+ * from the float32 f_k, sums in the order k = 0 .. K-1 (the numpy statement: bore_amd/ensemble.py, ensemble_score):
+ *   mu = (1/K) sum f_k;  d_k = f_k - mu;  v = (1/K) sum d_k^2;  sigma = sqrt(v + BORE_ENSEMBLE_VAR_FLOOR);
+ *   s = mu + beta sigma;  grad s = sum c_k grad f_k,  c_k = 1/K + beta d_k / (K sigma)
+ * The floor makes sigma smooth (no branch at 0; identical members: c_k = 1/K; K = 1: s = f + beta 1e-6); beta = 0:
+ * s = mu; beta = 0 and K = 1: the single-model objective.  The optimiser's objective is val = T(float32(+-s)) (float32)
+ * and grad = +-T'(float32(+-s)) grad s (float64), T and T' bore_mlp_value_and_input_grad's own; the screening ranks by
+ * s itself (T is monotone), descending, ties to the lower row: bore_screen_topk's rule.
+ *
+ * One workgroup serves one ensemble and stages the K members' padded LDS images once; a (row, member) pair is one
+ * wave's work, units over lanes, every sum one fmaf chain in ascending order: a row's bits do not depend on its
+ * neighbours, an ensemble's not on n_ens.  Refused before any HIP call, each bound by name, in this order: a bad
+ * descriptor; n_ens outside 1..65535; K outside 1..BORE_ENSEMBLE_MAX_MEMBERS; compute != float32; units[last] != 1;
+ * beta negative or not finite; the K images plus the pass workspace above 160 KB of LDS (16->32-32-32-1: 13 632 B an
+ * image, K = 8 fits, K = 16 does not; both byte counts in the message); then the entry point's own arguments (the
+ * restarts: bore_lbfgsb_minimize's verdicts and texts for the options and the box, D <= BORE_DIM_MAX, and the restart
+ * slots' LDS beside the images); last batch mode (bore_set_batch).
+ *   value + grad  X fp64 [n_ens][n_rows][D] -> val fp32 [n_ens][n_rows], grad fp64 [n_ens][n_rows][D].
+ *   screening     two launches: s of the candidates (X_init [n_ens][n_samples][D], or one [n_samples][D] with
+ *                 x_shared; n_samples <= BORE_STREAM_MAX_SAMPLES) into `score` -- stream-ordered scratch when NULL --
+ *                 then the library's selection stage (bore_stream_screen_topk's): idx and the fp64 rows x0.
+ *   restarts      bore_lbfgsb_minimize's results layout (x, fun, jac, info[5]); one launch, one problem per wave, up
+ *                 to four per workgroup (as many as have room for their slot beside the images), the driver of the
+ *                 streamed restarts around the pass of the value + grad entry point: every record equals the host
+ *                 build of lbfgsb.h fed bore_ensemble_value_and_input_grad's f and g, bit for bit.
+ *   plan query    host only.  maxcor == 0: the value + grad / screening launch; 1..32: the restart launch.  Fields:
+ *                 K, P_lds, image bytes, pass bytes, dynamic LDS bytes, waves that hold a problem, bytes of a slot,
+ *                 float offset of the ensemble's region, its carve (o_layout, o_pre, o_theta, o_x, o_wave,
+ *                 wave_floats, o_f, o_g, o_val, o_grad, total), the restart carve (o_box, o_vote, o_prob, o_dw, o_iw).
+ *                 batch_mode != 0: as under bore_set_batch.  The verdict is the return value.
+ * --------------------------------------------------------------------------------------------- */
+#define BORE_ENSEMBLE_MAX_MEMBERS 16
+#define BORE_ENSEMBLE_VAR_FLOOR 1e-12
+#define BORE_ENSEMBLE_PLAN_FIELDS 24
+
+int bore_ensemble_value_and_input_grad(const bore_mlp_desc *desc, int n_ens, int K, const float *theta,
+                                       const double *X, int64_t n_rows, double beta, int transform, int negate,
+                                       float *val, double *grad, void *stream);
+int bore_ensemble_screen_topk(const bore_mlp_desc *desc, int n_ens, int K, const float *theta,
+                              const double *X_init, int64_t n_samples, int x_shared, double beta,
+                              int num_starts, double *x0, int32_t *idx, float *score, void *stream);
+int bore_ensemble_lbfgsb_minimize(const bore_mlp_desc *desc, int n_ens, int K, const float *theta, double beta,
+                                  int transform, int negate, const double *x0, int num_starts,
+                                  const double *lb, const double *ub, const bore_lbfgsb_opts *opts,
+                                  double *x, double *fun, double *jac, int32_t *info, void *stream);
+int bore_ensemble_plan_query(const bore_mlp_desc *desc, int n_ens, int K, double beta, int maxcor,
+                             int batch_mode, int32_t *out, int n_out);
+
 #ifdef __cplusplus
 }
 #endif
